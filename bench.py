@@ -11,8 +11,13 @@ global B=32 over the ranks instead); with world > 1 every step also gathers the 
 and states to rank 0 over RCCL (BASELINE config 4's gather; --no-gather leaves it out and
 the JSON line says so), on a third stream, event-ordered and double-buffered (NsStep).
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries
-  roofline     for the dominant kernel (HIP events on its stream, over the timed steps)
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and
+prints the contract fields (metric, value, unit, ms_per_step, config ...) and nothing more.
+--dump-outputs DIR also writes what the last timed step returned to its caller as
+DIR/<name>.npy (the inputs are seeded, so two builds can be compared output for output).
+With --full the line also carries
+  roofline     for the dominant kernel (HIP events on its stream, over the timed steps; the
+               layer workloads take three extra steps under torch.profiler for it)
   cpu_baseline the oracle (torch-CPU restatement, bit-identical to the reference) timed on
                the host cores on a bounded sample (rank 0, N=1 only)
 """
@@ -51,7 +56,16 @@ def parse():
     p.add_argument("--overlap-steps", action="store_true",
                    help="layer workloads c2/c3/c5: consecutive steps on two alternating streams (step "
                         "k+1's emission beside step k's recursion; two batches in flight)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: per-op / per-kernel rooflines "
+                        "(event pairs inside the timed steps, a torch.profiler pass for the layer workloads), "
+                        "the gather's own time (world > 1) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy "
+                        "(float32 / float64; rank 0; at most 64 MB in all: larger outputs are a fixed, seeded "
+                        "sample of their rows)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0,
+                   help="--full: bounded CPU-baseline budget (0 = skip)")
     p.add_argument("--graph", action="store_true",
                    help="ns workload: replay each op from a captured HIP graph instead of launching it "
                         "eagerly (round 6: each op is one launch, eager is faster -- DESIGN.md §5)")
@@ -68,7 +82,7 @@ def parse():
     p.add_argument("--tv-only", choices=["fb", "vit"], default=None,
                    help="neural workload, diagnostic: run only the forward-backward or only the Viterbi call")
     p.add_argument("--no-kernel-profile", action="store_true",
-                   help="layer workloads: skip the torch.profiler pass that finds the dominant kernel")
+                   help="layer workloads, --full: skip the torch.profiler pass that finds the dominant kernel")
     p.add_argument("--no-follow", action="store_true",
                    help="ns workload, diagnostic: run the passes after the chains instead of the work "
                         "beside them in the chains' launches (csrc/follow.h); = --follow none")
@@ -83,6 +97,51 @@ def ns_follow(args):
     mode = "none" if args.no_follow else args.follow
     return {"default": (None, None), "none": (False, False), "fb": (True, False),
             "vit": (False, True), "all": (True, True)}[mode]
+
+
+DUMP_MAX_BYTES = 60 << 20   # of array data: the files of one dump stay under 64 MB in all
+
+
+def dump_outputs(dirname, named):
+    """Write `named` ((name, tensor) pairs: what the last timed step returned) as
+    dirname/<name>.npy, floating point as float32 (float64 stays), integers as float64.  When
+    the arrays together exceed DUMP_MAX_BYTES, the ones above an equal share are cut to a sample
+    of their rows (all leading dimensions flattened, the last kept), drawn without replacement by
+    a generator seeded with 0 and kept in order: the same rows for equal shapes and in every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, t in named:
+        t = t.detach().cpu()
+        arrs[name] = t.to(torch.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                          else torch.float64).numpy()
+    if sum(a.nbytes for a in arrs.values()) > DUMP_MAX_BYTES:
+        share = DUMP_MAX_BYTES // len(arrs)
+        large = [n for n, a in arrs.items() if a.nbytes > share]
+        share = (DUMP_MAX_BYTES - sum(a.nbytes for n, a in arrs.items() if n not in large)) // len(large)
+        for n in large:
+            rows = arrs[n].reshape(-1, arrs[n].shape[-1]) if arrs[n].ndim > 1 else arrs[n].reshape(-1, 1)
+            keep = max(1, min(len(rows), share // (rows.shape[1] * rows.itemsize)))
+            arrs[n] = rows[np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))]
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def flat_tensors(out, prefix="out"):
+    """(name, tensor) pairs of a step's return value: the tensors of nested tuples / lists in
+    order, named out0, out1, ... by position (None and non-tensors keep their number)"""
+    named, todo = [], [out]
+    flat = []
+    while todo:
+        o = todo.pop(0)
+        if isinstance(o, (tuple, list)):
+            todo = list(o) + todo
+        else:
+            flat.append(o)
+    for i, o in enumerate(flat):
+        if isinstance(o, torch.Tensor):
+            named.append((f"{prefix}{i}", o))
+    return named
 
 
 def spawn_ranks(args):
@@ -265,8 +324,8 @@ def layer_workload(args, rank, world, dev):
     """BASELINE configs 1/2/3/5 through the drop-in layers.
     One step = the config's reference call sequence on one synthetic batch (random-init layer
     of the named architecture, seed 0), inputs resident in HBM; each rank runs its own batch
-    (weak scaling).  Prints one JSON line with the dominant kernel's roofline and a bounded
-    CPU baseline (the oracle restatement, rank 0, N=1)."""
+    (weak scaling).  Prints one JSON line; with --full it carries the dominant kernel's
+    roofline and a bounded CPU baseline (the oracle restatement, rank 0, N=1)."""
     import pytorch_hmm_amd as ph
     from oracle import hmm_oracle as O
     wl = args.workload
@@ -447,8 +506,12 @@ def layer_workload(args, rank, world, dev):
         if side is not None:
             for s_ in side:
                 s_.wait_stream(main_s)
+        last = None
         for k in range(args.steps):
-            run(k)
+            if args.dump_outputs and k == args.steps - 1:
+                last = run(k)   # (kept only for the dump: a held result would change the allocator's reuse)
+            else:
+                run(k)
         if side is not None:
             for s_ in side:
                 main_s.wait_stream(s_)
@@ -465,6 +528,21 @@ def layer_workload(args, rank, world, dev):
     step_ms = e0.elapsed_time(e1) / args.steps
     frames = desc["batch_per_gpu"] * desc["seq_len"]
     value = frames * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, flat_tensors(last))
+    out = {"metric": f"frames/sec {desc['workload']}", "value": value, "unit": "frames/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+           "data": "synthetic: randn features, random-init layer (seed 0)",
+           "config": dict(desc, global_batch=desc["batch_per_gpu"] * world, parallelism=f"batch-sharded x{world}")}
+    if overlap:
+        out["step_overlap"] = ("consecutive steps on two alternating HIP streams (two batches in flight): "
+                               "step k+1's emission scoring runs beside step k's recursion")
+        out["ms_per_step_serial"] = serial_ms
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
     kroof = None
     if not args.no_kernel_profile:
         try:
@@ -487,16 +565,7 @@ def layer_workload(args, rank, world, dev):
         roof = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": None, "bytes_per_launch": bytes_,
                 "avg_launch_ms": step_ms, "note": "whole step time (HIP events) as the launch duration"}
-    out = {"metric": f"frames/sec {desc['workload']}", "value": value, "unit": "frames/s", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-           "data": "synthetic: randn features, random-init layer (seed 0)",
-           "config": dict(desc, global_batch=desc["batch_per_gpu"] * world, parallelism=f"batch-sharded x{world}"),
-           "roofline": roof}
-    if overlap:
-        out["step_overlap"] = ("consecutive steps on two alternating HIP streams (two batches in flight): "
-                               "step k+1's emission scoring runs beside step k's recursion")
-        out["ms_per_step_serial"] = serial_ms
+    out["roofline"] = roof
     if kroof is not None and roof is not kroof:
         out["kernel_profile"] = kroof
     if rank == 0 and world == 1 and args.cpu_seconds > 0:
@@ -771,10 +840,11 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    # per-op launch durations for the roofline: HIP events on each op's own stream around its
-    # graph replay, over the timed steps (an event pair costs the step ~1-2 us of queue work;
+    # --full: per-op launch durations for the roofline: HIP events on each op's own stream around
+    # its graph replay, over the timed steps (an event pair costs the step ~1-2 us of queue work;
     # the wall clock below is what `value` uses)
-    step.timing = {n: [] for n in (*step.names, "gather")}
+    if args.full:
+        step.timing = {n: [] for n in (*step.names, "gather")}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -787,20 +857,11 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    ev, step.timing = step.timing, None
-    fb_ms = sum(a.elapsed_time(b) for a, b in ev["fb"]) / len(ev["fb"])
-    vit_ms = sum(a.elapsed_time(b) for a, b in ev["vit"]) / len(ev["vit"])
-    gather_info = None
-    if ev["gather"]:
-        # the gather's own time on the communication stream (events around the dist.gather
-        # calls), and the bytes it moves into rank 0 per step: (world - 1) slices of posteriors
-        # (B*T*N fp32) + states (B*T int64); DESIGN.md §6 models it against xGMI
-        g_ms = [a.elapsed_time(b) for a, b in ev["gather"]]
-        rx = (world - 1) * B * T * (4 * N + 8)
-        gather_info = {"gather_ms": sum(g_ms) / len(g_ms), "gather_ms_max": max(g_ms),
-                       "bytes_into_rank0_per_step": rx,
-                       "rank0_rx_GBps": rx / (sum(g_ms) / len(g_ms) * 1e-3) / 1e9,
-                       "model_ms_at_153GBps_per_link": B * T * (4 * N + 8) / 153e9 * 1e3}
+    if rank == 0 and args.dump_outputs:
+        # what the callers of HMMPyTorch.forward_backward and viterbi_decode receive (hmm.py)
+        o = step.out[(step.k - 1) % step.nbuf]
+        dump_outputs(args.dump_outputs, list(zip(("posterior", "forward", "backward"), o["fb"][:3])) +
+                     list(zip(("states", "delta"), o["vit"][:2])))
     global_b = args.batch if args.strong else B * world
     value = global_b * T * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
@@ -808,7 +869,6 @@ def main():
     tdesc = {"left_to_right": "left_to_right(0.7)", "ergodic": "ergodic",
              "random": "random dense softmax(randn(N,N))",
              "trained": "trained HMMLayer(N) tables (3 Adam steps)"}[args.transition]
-    # roofline of the dominant op, algorithmic bytes per SURVEY.md §8(d)
     banded = plan is not None and getattr(plan, "_hmm355_banded", False)
     pair = banded and ops._use_pair(B, dev)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -816,23 +876,6 @@ def main():
     fb_fl, vit_fl = ns_follow(args)
     fb_follow = banded and not pair and fb_fl is not False and ops.fb_follow_default(fb_fl) and 3 * B <= cus
     vit_follow = banded and vit_fl is not False and N > 64 and 4 * B <= cus
-    if fb_ms >= vit_ms:
-        dom, dur_ms, bytes_per_launch = "forward_backward", fb_ms, 16 * N * B * T
-        kernels = ("fb_pair_kernel" if pair else
-                   "fb_recur_kernel (chains + posterior followers)" if fb_follow else "fb_recur_kernel + fb_posterior_kernel")
-    else:
-        dom, dur_ms, bytes_per_launch = "viterbi", vit_ms, (8 * N + 8) * B * T
-        kernels = ("vit_fwd_kernel (chains + log leaders + decode followers)" if vit_follow else
-                   "vit_log_obs_kernel + vit_fwd_kernel + vit_psi_kernel + vit_backtrace_kernel")
-    achieved = bytes_per_launch / (dur_ms * 1e-3) / 1e9
-    dom_traffic = traffic_fields(*profiled_traffic(dom, B, T, N, args.transition))
-    # both ops' fractions (north_star's target names forward-backward's)
-    op_roofline = {}
-    for name, ms, bpl in (("forward_backward", fb_ms, 16 * N * B * T), ("viterbi", vit_ms, (8 * N + 8) * B * T)):
-        a_ = bpl / (ms * 1e-3) / 1e9
-        op_roofline[name] = dict({"achieved": a_, "frac": a_ / HBM_PEAK_GBS, "bytes_per_launch": bpl,
-                                  "avg_launch_ms": ms},
-                                 **traffic_fields(*profiled_traffic(name, B, T, N, args.transition)))
     out = {
         "metric": "frames/sec forward-backward+Viterbi, B=32 T=2000 N=128, 1/2/4/8 GPU",
         "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -852,13 +895,53 @@ def main():
                                  "chains + posterior followers in one launch" if fb_follow else "two-kernel"),
                    "viterbi_kernel": ("chains + log leaders + decode followers in one launch" if vit_follow else
                                       "log pass + chain + psi pass + backtrace")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    ev, step.timing = step.timing, None
+    fb_ms = sum(a.elapsed_time(b) for a, b in ev["fb"]) / len(ev["fb"])
+    vit_ms = sum(a.elapsed_time(b) for a, b in ev["vit"]) / len(ev["vit"])
+    gather_info = None
+    if ev["gather"]:
+        # the gather's own time on the communication stream (events around the dist.gather
+        # calls), and the bytes it moves into rank 0 per step: (world - 1) slices of posteriors
+        # (B*T*N fp32) + states (B*T int64); DESIGN.md §6 models it against xGMI
+        g_ms = [a.elapsed_time(b) for a, b in ev["gather"]]
+        rx = (world - 1) * B * T * (4 * N + 8)
+        gather_info = {"gather_ms": sum(g_ms) / len(g_ms), "gather_ms_max": max(g_ms),
+                       "bytes_into_rank0_per_step": rx,
+                       "rank0_rx_GBps": rx / (sum(g_ms) / len(g_ms) * 1e-3) / 1e9,
+                       "model_ms_at_153GBps_per_link": B * T * (4 * N + 8) / 153e9 * 1e3}
+    # roofline of the dominant op, algorithmic bytes per SURVEY.md §8(d)
+    if fb_ms >= vit_ms:
+        dom, dur_ms, bytes_per_launch = "forward_backward", fb_ms, 16 * N * B * T
+        kernels = ("fb_pair_kernel" if pair else
+                   "fb_recur_kernel (chains + posterior followers)" if fb_follow else "fb_recur_kernel + fb_posterior_kernel")
+    else:
+        dom, dur_ms, bytes_per_launch = "viterbi", vit_ms, (8 * N + 8) * B * T
+        kernels = ("vit_fwd_kernel (chains + log leaders + decode followers)" if vit_follow else
+                   "vit_log_obs_kernel + vit_fwd_kernel + vit_psi_kernel + vit_backtrace_kernel")
+    achieved = bytes_per_launch / (dur_ms * 1e-3) / 1e9
+    dom_traffic = traffic_fields(*profiled_traffic(dom, B, T, N, args.transition))
+    # both ops' fractions (north_star's target names forward-backward's)
+    op_roofline = {}
+    for name, ms, bpl in (("forward_backward", fb_ms, 16 * N * B * T), ("viterbi", vit_ms, (8 * N + 8) * B * T)):
+        a_ = bpl / (ms * 1e-3) / 1e9
+        op_roofline[name] = dict({"achieved": a_, "frac": a_ / HBM_PEAK_GBS, "bytes_per_launch": bpl,
+                                  "avg_launch_ms": ms},
+                                 **traffic_fields(*profiled_traffic(name, B, T, N, args.transition)))
+    out.update({
         "op_ms": {"forward_backward": fb_ms, "viterbi": vit_ms},
         "roofline": {"bound": "hbm", "kernel": dom, "kernels": kernels, "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      **dom_traffic,
                      "bytes_per_launch": bytes_per_launch, "avg_launch_ms": dur_ms},
         "roofline_ops": op_roofline,
-    }
+    })
     if gather_info is not None:
         out["gather"] = gather_info
     if rank == 0 and world == 1 and args.cpu_seconds > 0:

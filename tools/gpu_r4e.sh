@@ -1,11 +1,11 @@
 #!/bin/bash
 # round 4: dense-chain scheduling + layer workloads (c3, random NS)
 set -o pipefail
-mkdir -p gpurun_out
+export OUT=${OUT:-results}; mkdir -p "$OUT"   # logs and profiles land here
 run() {
   tag=$1; shift
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 "$@" > gpurun_out/r4g_$tag.log 2>&1 || exit 1
-  python - gpurun_out/r4g_$tag.log <<'PY'
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 "$@" > $OUT/r4g_$tag.log 2>&1 || exit 1
+  python - $OUT/r4g_$tag.log <<'PY'
 import json,sys
 for l in open(sys.argv[1]):
     if l.startswith("{"):
