@@ -93,7 +93,10 @@ def plan_info(plan: Optional[Tensor]) -> dict:
             return "dense"
         return f"banded(W={w}, toeplitz {td0}..{td0 + tw - 1})" if tw > 0 else f"banded(W={w})"
     col = name(wc, tcw, tcd0)
-    return {"forward": col, "viterbi": col, "backward": name(wr, trw, trd0)}
+    # beside the names, the raw header (BandDesc wc .. wrp, tcd0 .. trw, uafl)
+    return {"forward": col, "viterbi": col, "backward": name(wr, trw, trd0),
+            "wc": wc, "wr": wr, "wcp": h[2], "wrp": h[3], "tcd0": tcd0, "tcw": tcw, "trd0": trd0, "trw": trw,
+            "uniform_floor": h[7176]}
 
 
 _CUS = {}
