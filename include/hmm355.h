@@ -17,8 +17,10 @@
  *     (and may be captured into a hipGraph).
  *   - Return 0 on success, a negative HMM355_E* code on a rejected argument (nothing is
  *     launched), or a positive hipError_t if a launch failed.  hmm355_strerror() names it.
- *   - Supported sizes: 1 <= N <= 256 states (padded internally to 64/128/256),
- *     T >= 1, B >= 0 (B == 0 is a no-op).
+ *   - Supported sizes: T >= 1, B >= 0 (B == 0 is a no-op).  States: 1 <= N <= 256 for the
+ *     recursions that run one workgroup per sequence (padded internally to 64/128/256), and
+ *     1 <= N <= 4096 for the batch-tiled hmm355_viterbi_wide_f32 /
+ *     hmm355_forward_backward_wide_f32 (one launch per time step, no padding).
  */
 #ifndef HMM355_H
 #define HMM355_H
@@ -32,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside [1, 256]                                  */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]) */
 #define HMM355_E_SHAPE (-3)     /* T < 1, or a size product overflows                  */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024]                  */
@@ -197,6 +199,35 @@ int hmm355_viterbi_f32(const float* obs, int obs_mode, const float* log_P, const
                        int B, int T, int N, int64_t* states, float* log_delta,
                        float* final_score, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Batch-tiled ("wide") Viterbi and forward-backward, 1 <= N <= 4096 (csrc/wide.hip).  Arguments,
+ * conventions and results as hmm355_viterbi_f32 / hmm355_forward_backward_f32 (the Viterbi
+ * trellis and path are bit-identical to theirs; OBS_PROB decodes use the same correctly
+ * rounded log(x + 1e-8)); N outside [1, 4096] returns HMM355_E_STATES and the size queries 0.
+ * All B sequences share log_P, so one time step of the batch is a (B,N).(N,N) product tiled over
+ * 64 output columns and 2 sequences per workgroup; consecutive time steps are separate launches
+ * on `stream` (T + 1 or T + 2 launches for a decode, T + 3 or T + 4 for forward-backward), so a call's host time
+ * grows with T.  No plan, no log_beta_T (gradients stay with N <= 256), no padding: the
+ * workspace rows have stride N.
+ *   Viterbi workspace: psi (B,T,N) uint16 | log-emissions (B,T,N) fp32 (OBS_PROB only).
+ *   Forward-backward workspace: A = exp(log_P) | A^T (N,N) | U | V (B,T,N) raw alpha / beta rows
+ *   | SA | SB | M (B,T) fp32 | CLA | CLB (B,T) fp64, pieces 256-B aligned.  U_{t+1} =
+ *   (A^T (U_t / SA_t)) e_{t+1} with SA_t = sum_j U_t[j]; V_{t-1} = A (e_t V_t / SB_t) with SB_t =
+ *   sum_j e_t[j] V_t[j]; e_t as in hmm355_forward_backward_ex_f32 (x + 1e-8, or exp(x - M_t));
+ *   log alpha_t = log U_t + CLA_t, log beta_t = log V_t + CLB_t (the log-scales, summed in fp64).
+ * ------------------------------------------------------------------------------ */
+size_t hmm355_viterbi_wide_workspace_bytes(int B, int T, int N, int obs_mode);
+int hmm355_viterbi_wide_f32(const float* obs, int obs_mode, const float* log_P, const float* init,
+                            int B, int T, int N, int64_t* states, float* log_delta,
+                            float* final_score, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t hmm355_fb_wide_workspace_bytes(int B, int T, int N);
+int hmm355_forward_backward_wide_f32(const float* obs, int obs_mode, const float* log_P,
+                                     const float* log_p0, int B, int T, int N, unsigned out_mask,
+                                     float* posterior, float* forward, float* backward,
+                                     float* loglik, float* lik_ref, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Diagonal-covariance Gaussian-mixture emission scorer.  Replaces

@@ -23,6 +23,8 @@ FORM_GENERAL = 0x1  # HMM355_FORM_GENERAL
 FORM_SERIAL_WALK = 0x2  # HMM355_FORM_SERIAL_WALK
 FB_FORWARD = 2
 FB_BACKWARD = 4
+NARROW_MAX_STATES = 256  # the chains of fb.hip / viterbi.hip (one workgroup per sequence)
+WIDE_MAX_STATES = 4096   # the batch-tiled *_wide entry points (csrc/wide.hip)
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -42,6 +44,8 @@ EXPORTS = (
     "hmm355_plan_bytes", "hmm355_plan_f32", "hmm355_plan_ex_f32", "hmm355_plan_banded",
     "hmm355_forward_backward_plan_f32", "hmm355_viterbi_plan_f32", "hmm355_viterbi_plan_ex_f32",
     "hmm355_fb_adjoint_f32", "hmm355_tv_fb_adjoint_f32",
+    "hmm355_viterbi_wide_workspace_bytes", "hmm355_viterbi_wide_f32",
+    "hmm355_fb_wide_workspace_bytes", "hmm355_forward_backward_wide_f32",
 )
 
 _lib = None
@@ -123,6 +127,12 @@ def lib():
     LL = ctypes.c_longlong
     L.hmm355_tv_fb_adjoint_f32.argtypes = [P, P, LL, LL, P, P, P, P, I, I, I, P, P, P]
     L.hmm355_tv_fb_adjoint_f32.restype = I
+    L.hmm355_viterbi_wide_workspace_bytes.argtypes, L.hmm355_viterbi_wide_workspace_bytes.restype = [I, I, I, I], S
+    L.hmm355_viterbi_wide_f32.argtypes = [P, I, P, P, I, I, I, P, P, P, P, S, P]
+    L.hmm355_viterbi_wide_f32.restype = I
+    L.hmm355_fb_wide_workspace_bytes.argtypes, L.hmm355_fb_wide_workspace_bytes.restype = [I, I, I], S
+    L.hmm355_forward_backward_wide_f32.argtypes = [P, I, P, P, I, I, I, U, P, P, P, P, P, P, S, P]
+    L.hmm355_forward_backward_wide_f32.restype = I
     _lib = L
     return L
 

@@ -51,6 +51,16 @@ def fb_layout(B, T, N):
     return dict(zip(FB_PIECES, out))
 
 
+def _require_narrow(N, what):
+    """The adjoints read the scaled rows and step factors of the one-workgroup-per-sequence
+    chains (fb_layout); the batch-tiled form above 256 states keeps another layout and takes no
+    terminal backward vector, so gradients stop at 256 states."""
+    if N > nat.NARROW_MAX_STATES:
+        raise NotImplementedError(
+            f"{what} is implemented for at most {nat.NARROW_MAX_STATES} states (got {N}): above that the "
+            "forward-backward runs without autograd support (call it under torch.no_grad() / on detached inputs)")
+
+
 def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_mask=None, plan=None):
     """One hmm355_forward_backward_plan_f32 call; returns (posterior|None, loglik, lik_ref, U, V,
     LA, LB), or with `out_mask` ((posterior, forward, backward) per the mask, loglik, lik_ref, U,
@@ -102,6 +112,7 @@ class SequenceLogLik(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, log_P, log_p0, obs_mode, kind, plan=None):
+        _require_narrow(obs.shape[-1], "the gradient of the sequence log-likelihood")
         nat.require_gpu(obs, log_P, log_p0)
         obs_c, lP, l0 = (t.detach().to(torch.float32).contiguous() for t in (obs, log_P, log_p0))
         _, loglik, lik_ref, *_ = _run_fb(obs_c, lP, l0, obs_mode, plan=plan)
@@ -423,6 +434,7 @@ def tv_forward_backward_with_grad(log_obs, log_A, log_p0, out_mask):
 
 def forward_backward_with_grad(obs, log_P, log_p0, obs_mode, out_mask, plan=None):
     """Differentiable forward-backward outputs (tuple per out_mask: posterior, forward, backward)."""
+    _require_narrow(obs.shape[-1], "the gradient of the forward-backward outputs")
     return ForwardBackwardFn.apply(obs, log_P, log_p0, obs_mode, out_mask, plan)
 
 

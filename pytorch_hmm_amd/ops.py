@@ -32,6 +32,8 @@ FORM_GENERAL = nat.FORM_GENERAL
 FORM_SERIAL_WALK = nat.FORM_SERIAL_WALK
 FB_FORWARD = nat.FB_FORWARD
 FB_BACKWARD = nat.FB_BACKWARD
+NARROW_MAX_STATES = nat.NARROW_MAX_STATES
+WIDE_MAX_STATES = nat.WIDE_MAX_STATES
 
 _EMPTY = (0,)
 
@@ -45,7 +47,13 @@ def _workspace(nbytes, device):
 
 
 # ------------------------------------------------------------------ forward-backward
-def make_plan(log_P: Tensor, read_banded: bool = True, dense: bool = False) -> Tensor:
+def _use_wide(N: int, wide: Optional[bool]) -> bool:
+    """The batch-tiled form (csrc/wide.hip, one launch per time step, N <= 4096): above 256 states
+    unless the caller says otherwise; wide=True forces it at any N (parity tests)."""
+    return N > NARROW_MAX_STATES if wide is None else bool(wide)
+
+
+def make_plan(log_P: Tensor, read_banded: bool = True, dense: bool = False) -> Optional[Tensor]:
     """Measure log_P's banded structure once (hmm355_plan_ex_f32) into a device byte tensor that
     forward_backward / viterbi accept as `plan` (valid while log_P is unchanged).  dense=True
     (HMM355_PLAN_DENSE) makes a plan that selects the dense chains whatever the structure (the
@@ -57,7 +65,12 @@ def make_plan(log_P: Tensor, read_banded: bool = True, dense: bool = False) -> T
     training step, where log_P changes each call) that read is skipped and the plan's host
     word stays unknown (None): forward_backward takes the two-kernel path, whose chains branch
     on the device-side structure, and viterbi asks for psi followers, which return at once on
-    a banded plan (vit_kern.h vit_psi_follow) -- so the call stays asynchronous."""
+    a banded plan (vit_kern.h vit_psi_follow) -- so the call stays asynchronous.
+
+    Above 256 states there is no plan (None, no native call): forward_backward / viterbi take
+    the batch-tiled form there, which reads log_P as it is."""
+    if log_P.shape[0] > NARROW_MAX_STATES:
+        return None
     nat.require_gpu(log_P)
     log_P = _f32c(log_P)
     N = log_P.shape[0]
@@ -126,10 +139,13 @@ def _use_pair(B: int, dev) -> bool:
 @torch.library.custom_op("hmm355::forward_backward", mutates_args=())
 def forward_backward(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int,
                      out_mask: int, plan: Optional[Tensor] = None, pair: Optional[bool] = None,
-                     follow: Optional[bool] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+                     follow: Optional[bool] = None,
+                     wide: Optional[bool] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """pair / follow (None = chosen from the batch and the plan): with a host-known banded plan,
     `pair` runs both chains of a sequence in one workgroup (HMM355_FB_PAIR, large batches) and
-    otherwise `follow` forms the posterior inside the chains' launch (HMM355_FB_PLAN_BANDED)."""
+    otherwise `follow` forms the posterior inside the chains' launch (HMM355_FB_PLAN_BANDED).
+    wide (None = N > 256): the batch-tiled form (hmm355_forward_backward_wide_f32, N <= 4096),
+    which ignores plan / pair / follow."""
     nat.require_gpu(obs, log_P, log_p0)
     obs, log_P, log_p0 = _f32c(obs), _f32c(log_P), _f32c(log_p0)
     B, T, N = obs.shape
@@ -141,6 +157,16 @@ def forward_backward(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int,
     loglik = torch.empty(B, device=dev)
     lik_ref = torch.empty(B, device=dev)
     if B == 0:
+        return post, fwd, bwd, loglik, lik_ref
+    if _use_wide(N, wide):
+        ws = _workspace(L.hmm355_fb_wide_workspace_bytes(B, T, N), dev)
+        with torch.cuda.device(dev):
+            nat.check(L.hmm355_forward_backward_wide_f32(
+                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), B, T, N, out_mask & 7,
+                nat.ptr(post) if out_mask & FB_POSTERIOR else None,
+                nat.ptr(fwd) if out_mask & FB_FORWARD else None,
+                nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
+                nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
         return post, fwd, bwd, loglik, lik_ref
     nbytes = L.hmm355_fb_workspace_bytes(B, T, N)
     ws = _workspace(nbytes, dev)
@@ -161,7 +187,7 @@ def forward_backward(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int,
 
 
 @forward_backward.register_fake
-def _(obs, log_P, log_p0, obs_mode, out_mask, plan=None, pair=None, follow=None):
+def _(obs, log_P, log_p0, obs_mode, out_mask, plan=None, pair=None, follow=None, wide=None):
     B, T, N = obs.shape
     mk = lambda bit: obs.new_empty((B, T, N) if out_mask & bit else _EMPTY)
     return mk(FB_POSTERIOR), mk(FB_FORWARD), mk(FB_BACKWARD), obs.new_empty(B), obs.new_empty(B)
@@ -170,10 +196,13 @@ def _(obs, log_P, log_p0, obs_mode, out_mask, plan=None, pair=None, follow=None)
 # ---------------------------------------------------------------------------- Viterbi
 @torch.library.custom_op("hmm355::viterbi", mutates_args=())
 def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
-            plan: Optional[Tensor] = None, follow: Optional[bool] = None) -> Tuple[Tensor, Tensor, Tensor]:
+            plan: Optional[Tensor] = None, follow: Optional[bool] = None,
+            wide: Optional[bool] = None) -> Tuple[Tensor, Tensor, Tensor]:
     """follow (None = on): with a plan, the work beside the chain inside its launch -- for a
     host-known banded plan the log leaders and the decode follower (HMM355_VIT_PLAN_BANDED), for a
-    dense one the psi followers (HMM355_VIT_PLAN_DENSE)."""
+    dense one the psi followers (HMM355_VIT_PLAN_DENSE).
+    wide (None = N > 256): the batch-tiled form (hmm355_viterbi_wide_f32, N <= 4096), which
+    ignores plan / follow."""
     nat.require_gpu(obs, log_P, init)
     obs, log_P, init = _f32c(obs), _f32c(log_P), _f32c(init)
     B, T, N = obs.shape
@@ -183,6 +212,13 @@ def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
     delta = torch.empty((B, T, N), device=dev)
     final = torch.empty(B, device=dev)
     if B == 0:
+        return states, delta, final
+    if _use_wide(N, wide):
+        ws = _workspace(L.hmm355_viterbi_wide_workspace_bytes(B, T, N, obs_mode), dev)
+        with torch.cuda.device(dev):
+            nat.check(L.hmm355_viterbi_wide_f32(
+                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), B, T, N, nat.ptr(states), nat.ptr(delta),
+                nat.ptr(final), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
         return states, delta, final
     ws = _workspace(L.hmm355_viterbi_workspace_bytes_ex(B, T, N, obs_mode), dev)
     flags = 0
@@ -202,7 +238,7 @@ def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
 
 
 @viterbi.register_fake
-def _(obs, log_P, init, obs_mode, plan=None, follow=None):
+def _(obs, log_P, init, obs_mode, plan=None, follow=None, wide=None):
     B, T, N = obs.shape
     return (obs.new_empty((B, T), dtype=torch.int64), obs.new_empty((B, T, N)), obs.new_empty(B))
 
