@@ -35,7 +35,7 @@ extern "C" {
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
 #define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]) */
-#define HMM355_E_SHAPE (-3)     /* T < 1, or a size product overflows                  */
+#define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024]                  */
 
@@ -419,6 +419,57 @@ int hmm355_stream_greedy_f32(const float* emis, const float* log_T, const int* p
 int hmm355_stream_beam_f32(const float* emis, const float* log_T, int B, int T, int N, int K,
                            int live_max, float* hyp_score, int* hyp_last, int* hyp_count, const int* first,
                            int16_t* parent, int16_t* hstate, int64_t* states, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Dynamic time warping over a distance matrix (csrc/dtw.hip).  Replace compute_dtw_path
+ * (alignment/dtw.py:61-152), the soft-DTW loop of DTWAligner._soft_dtw_align (dtw.py:277-299) and
+ * the autograd through it.  One workgroup per pair, one launch per call.
+ *   dist   (B,N,M) fp32 row-major distance matrices; +inf entries are allowed (a band), NaN is not
+ *   n_len, m_len  (B) int32 or NULL: pair b uses the top-left n_len[b] x m_len[b] corner
+ *          (NULL = N / M; values are clamped to [1, N] / [1, M])
+ * Any N, M >= 1, B >= 0 (B == 0 launches nothing); N < 1 or M < 1 or a size that overflows
+ * returns HMM355_E_SHAPE and the size query 0.
+ *
+ * hmm355_dtw_f32: hard DTW.  C[0,0] = D[0,0]; predecessors that do not exist are left out.
+ *   HMM355_DTW_SYMMETRIC / _ASYMMETRIC  C[i,j] = D[i,j] + min(C[i-1,j-1], C[i-1,j], C[i,j-1])
+ *          (the reference's asymmetric min(c + d) has the same bits: the fp32 add is monotone)
+ *   HMM355_DTW_RABINER_JUANG            C[i,j] = min(C[i-1,j-1] + 2 D[i,j], C[i-1,j] + D[i,j],
+ *                                                    C[i,j-1] + D[i,j])
+ *   The cost matrix is bit-identical to the reference's.  Any other pattern: HMM355_E_ARG.
+ *   flags  HMM355_DTW_PATH: also backtrace from (n-1, m-1) to (0,0), at each step to the
+ *          predecessor of smallest raw cost, ties in the order (i-1,j-1), (i-1,j), (i,j-1)
+ *          (dtw.py:127-143).  path_i / path_j / path_len must then be given.
+ *   cost_matrix (B,N,M) or NULL; cells outside a pair's corner are +inf.  With NULL and no path
+ *          only `total` is produced and no N x M table is written.
+ *   total  (B): C[n-1, m-1] (+inf when the end cell is unreachable)
+ *   path_i, path_j (B, N+M-1) int32 in path order from index 0, -1 past the end; path_len (B)
+ *   workspace >= hmm355_dtw_workspace_bytes(B, N, M, flags), 16-byte aligned: a row buffer
+ *          (B, 4 ceil(M/4)) fp32 | with HMM355_DTW_PATH the directions, one byte per row and four
+ *          columns (B, N, ceil(M/4)) | the walk end-to-start, 2 x (B, N+M-1) int32.
+ *
+ * hmm355_softdtw_f32: R (B,N+1,M+1) with R[0,0] = 0, the rest of row 0 and column 0 +inf,
+ *   R[i,j] = D[i-1,j-1] + softmin_gamma(R[i-1,j-1], R[i-1,j], R[i,j-1]),
+ *   softmin_gamma(c) = m - gamma log sum exp(-(c - m) / gamma), m = min c (+inf when m is);
+ *   total (B) = R[n,m]; entries of R outside a pair's corner are +inf.  gamma must be > 0 and
+ *   finite (HMM355_E_ARG).
+ * hmm355_softdtw_grad_f32: E (B,N,M) = d total / d dist from the R hmm355_softdtw_f32 stored
+ *   (Cuturi & Blondel 2017, Algorithm 2, its factors evaluated as the softmin's weights, which R
+ *   alone determines; dist must be given and is not read); 0 outside a pair's corner and on
+ *   cells R marks unreachable.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_DTW_SYMMETRIC 0
+#define HMM355_DTW_ASYMMETRIC 1
+#define HMM355_DTW_RABINER_JUANG 2
+#define HMM355_DTW_PATH 0x1u
+size_t hmm355_dtw_workspace_bytes(int B, int N, int M, unsigned flags);
+int hmm355_dtw_f32(const float* dist, const int* n_len, const int* m_len, int B, int N, int M,
+                   int pattern, unsigned flags, float* cost_matrix, float* total, int* path_i,
+                   int* path_j, int* path_len, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int hmm355_softdtw_f32(const float* dist, const int* n_len, const int* m_len, int B, int N, int M,
+                       float gamma, float* R, float* total, void* stream);
+int hmm355_softdtw_grad_f32(const float* dist, const float* R, const int* n_len, const int* m_len,
+                            int B, int N, int M, float gamma, float* E, void* stream);
 
 #ifdef __cplusplus
 }

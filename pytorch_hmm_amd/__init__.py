@@ -23,3 +23,8 @@ from .streaming import AdaptiveLatencyController, StreamingHMMProcessor, Streami
 __all__ += ["HMMLayer", "GaussianHMMLayer", "MixtureGaussianHMMLayer", "HSMMLayer", "NeuralHMM",
             "ContextualNeuralHMM", "DurationModel", "SemiMarkovHMM", "AdaptiveDurationHSMM",
             "StreamingHMMProcessor", "StreamingResult", "AdaptiveLatencyController"]
+
+from . import alignment
+from .alignment import ConstrainedDTWAligner, DTWAligner
+
+__all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner"]

@@ -25,6 +25,8 @@ FB_FORWARD = 2
 FB_BACKWARD = 4
 NARROW_MAX_STATES = 256  # the chains of fb.hip / viterbi.hip (one workgroup per sequence)
 WIDE_MAX_STATES = 4096   # the batch-tiled *_wide entry points (csrc/wide.hip)
+DTW_SYMMETRIC, DTW_ASYMMETRIC, DTW_RABINER_JUANG = 0, 1, 2  # HMM355_DTW_* step patterns
+DTW_PATH = 0x1  # HMM355_DTW_PATH
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -46,6 +48,7 @@ EXPORTS = (
     "hmm355_fb_adjoint_f32", "hmm355_tv_fb_adjoint_f32",
     "hmm355_viterbi_wide_workspace_bytes", "hmm355_viterbi_wide_f32",
     "hmm355_fb_wide_workspace_bytes", "hmm355_forward_backward_wide_f32",
+    "hmm355_dtw_workspace_bytes", "hmm355_dtw_f32", "hmm355_softdtw_f32", "hmm355_softdtw_grad_f32",
 )
 
 _lib = None
@@ -133,6 +136,10 @@ def lib():
     L.hmm355_fb_wide_workspace_bytes.argtypes, L.hmm355_fb_wide_workspace_bytes.restype = [I, I, I], S
     L.hmm355_forward_backward_wide_f32.argtypes = [P, I, P, P, I, I, I, U, P, P, P, P, P, P, S, P]
     L.hmm355_forward_backward_wide_f32.restype = I
+    L.hmm355_dtw_workspace_bytes.argtypes, L.hmm355_dtw_workspace_bytes.restype = [I, I, I, U], S
+    L.hmm355_dtw_f32.argtypes, L.hmm355_dtw_f32.restype = [P, P, P, I, I, I, I, U, P, P, P, P, P, P, S, P], I
+    L.hmm355_softdtw_f32.argtypes, L.hmm355_softdtw_f32.restype = [P, P, P, I, I, I, F, P, P, P], I
+    L.hmm355_softdtw_grad_f32.argtypes, L.hmm355_softdtw_grad_f32.restype = [P, P, P, P, I, I, I, F, P, P], I
     _lib = L
     return L
 

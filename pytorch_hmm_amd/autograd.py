@@ -526,3 +526,30 @@ class ViterbiScore(torch.autograd.Function):
             grad_T.index_add_(0, idx, g.view(B, 1).expand(B, T - 1).reshape(-1))
         grad_init = torch.zeros(S, device=g.device).index_add_(0, states[:, 0], g)
         return grad_lp, grad_T.view(S, S), grad_init, None
+
+
+class SoftDTW(torch.autograd.Function):
+    """total (B) = soft-DTW of the distance matrices dist (B,N,M) (ops.soft_dtw), differentiable in
+    dist: the backward is the reverse wavefront of Cuturi & Blondel's Algorithm 2 over the saved
+    dist and R (ops.soft_dtw_grad), E * grad_total.  Replaces the reference's autograd through the
+    per-cell loop of DTWAligner._soft_dtw_align (alignment/dtw.py:277-299); the gradient reaches
+    the sequences through the distance matrix by plain torch autograd.
+
+        total = SoftDTW.apply(dist, gamma, n_len, m_len)      # n_len / m_len (B) or None
+    """
+
+    @staticmethod
+    def forward(ctx, dist, gamma, n_len=None, m_len=None):
+        from . import ops
+        d = dist.detach()
+        R, total = ops.soft_dtw(d, float(gamma), n_len, m_len)
+        ctx.save_for_backward(d, R)
+        ctx.gamma, ctx.lens = float(gamma), (n_len, m_len)
+        return total
+
+    @staticmethod
+    def backward(ctx, grad_total):
+        from . import ops
+        d, R = ctx.saved_tensors
+        E = ops.soft_dtw_grad(d, R, ctx.gamma, *ctx.lens)
+        return E * grad_total.to(E.dtype)[:, None, None], None, None, None

@@ -13,6 +13,10 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.tv_forward_backward(log_obs, log_A, log_p0, out_mask)
       -> (posterior, forward, backward, loglik, lik_ref)
   torch.ops.hmm355.tv_viterbi(log_obs, log_A, init) -> (states, log_delta)
+  torch.ops.hmm355.dtw(dist, pattern, n_len, m_len, want_cost, want_path)
+      -> (cost_matrix, total, path_i, path_j, path_len)
+  torch.ops.hmm355.soft_dtw(dist, gamma, n_len, m_len) -> (R, total)
+  torch.ops.hmm355.soft_dtw_grad(dist, R, gamma, n_len, m_len) -> E
 """
 from typing import Optional, Tuple
 
@@ -564,3 +568,129 @@ def stream_beam(emis: Tensor, log_T: Tensor, beam_width: int, hyp_score: Tensor,
             nat.ptr(hyp_count), nat.ptr(first), nat.ptr(parent), nat.ptr(hstate), nat.ptr(states),
             nat.stream_of(dev)))
     return states, parent, hstate
+
+
+# ------------------------------------------------------------------ dynamic time warping
+DTW_SYMMETRIC = nat.DTW_SYMMETRIC
+DTW_ASYMMETRIC = nat.DTW_ASYMMETRIC
+DTW_RABINER_JUANG = nat.DTW_RABINER_JUANG
+DTW_PATTERNS = {"symmetric": DTW_SYMMETRIC, "asymmetric": DTW_ASYMMETRIC, "rabiner_juang": DTW_RABINER_JUANG}
+
+
+def dtw_pattern(step_pattern) -> int:
+    """The HMM355_DTW_* constant of a reference step-pattern name (or of the constant itself)."""
+    if isinstance(step_pattern, str):
+        if step_pattern not in DTW_PATTERNS:
+            raise ValueError(f"Unknown step pattern: {step_pattern}")
+        return DTW_PATTERNS[step_pattern]
+    return int(step_pattern)
+
+
+def _dtw_lens(dist, n_len, m_len):
+    nat.require_gpu(dist, n_len, m_len)
+    if dist.dim() != 3:
+        raise ValueError(f"dist must be (B, N, M); got {tuple(dist.shape)}")
+    B = dist.shape[0]
+    out = []
+    for name, t in (("n_len", n_len), ("m_len", m_len)):
+        if t is not None:
+            if t.numel() != B:
+                raise ValueError(f"{name} must hold one length per pair ({B}); got {tuple(t.shape)}")
+            t = t.to(torch.int32).contiguous()
+        out.append(t)
+    return out
+
+
+@torch.library.custom_op("hmm355::dtw", mutates_args=())
+def dtw(dist: Tensor, pattern: int, n_len: Optional[Tensor] = None, m_len: Optional[Tensor] = None,
+        want_cost: bool = True, want_path: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Hard DTW of B distance matrices (B,N,M) in one launch (hmm355_dtw_f32, csrc/dtw.hip).
+    pattern: DTW_SYMMETRIC / DTW_ASYMMETRIC / DTW_RABINER_JUANG (dtw_pattern(name)).  n_len / m_len
+    (B) restrict pair b to its top-left corner.  Returns (cost_matrix (B,N,M), +inf outside a
+    pair's corner; total (B); path_i, path_j (B,N+M-1) int32, -1 past the end; path_len (B) int32);
+    want_cost=False / want_path=False return empty tensors in their places (with both off no
+    N x M table is written).  A band is +inf entries in dist."""
+    n_len, m_len = _dtw_lens(dist, n_len, m_len)
+    dist = _f32c(dist)
+    B, N, M = dist.shape
+    dev = dist.device
+    if N < 1 or M < 1:
+        raise ValueError(f"dist must have at least one row and one column; got {tuple(dist.shape)}")
+    P = N + M - 1
+    cost = torch.empty((B, N, M) if want_cost else _EMPTY, device=dev)
+    total = torch.empty(B, device=dev)
+    path_i = torch.empty((B, P) if want_path else _EMPTY, dtype=torch.int32, device=dev)
+    path_j = torch.empty((B, P) if want_path else _EMPTY, dtype=torch.int32, device=dev)
+    path_len = torch.empty(B if want_path else 0, dtype=torch.int32, device=dev)
+    if B == 0:
+        return cost, total, path_i, path_j, path_len
+    L = nat.lib()
+    flags = nat.DTW_PATH if want_path else 0
+    ws = _workspace(L.hmm355_dtw_workspace_bytes(B, N, M, flags), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_dtw_f32(
+            nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, int(pattern), flags,
+            nat.ptr(cost) if want_cost else None, nat.ptr(total),
+            nat.ptr(path_i) if want_path else None, nat.ptr(path_j) if want_path else None,
+            nat.ptr(path_len) if want_path else None, nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return cost, total, path_i, path_j, path_len
+
+
+@dtw.register_fake
+def _(dist, pattern, n_len=None, m_len=None, want_cost=True, want_path=True):
+    B, N, M = dist.shape
+    P = N + M - 1
+    i32 = torch.int32
+    return (dist.new_empty((B, N, M) if want_cost else _EMPTY, dtype=torch.float32),
+            dist.new_empty(B, dtype=torch.float32),
+            dist.new_empty((B, P) if want_path else _EMPTY, dtype=i32),
+            dist.new_empty((B, P) if want_path else _EMPTY, dtype=i32),
+            dist.new_empty(B if want_path else 0, dtype=i32))
+
+
+@torch.library.custom_op("hmm355::soft_dtw", mutates_args=())
+def soft_dtw(dist: Tensor, gamma: float, n_len: Optional[Tensor] = None,
+             m_len: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Soft-DTW of B distance matrices (hmm355_softdtw_f32): R (B,N+1,M+1) and total (B) = R[n,m].
+    No gradient of its own: autograd.SoftDTW saves R and runs soft_dtw_grad."""
+    n_len, m_len = _dtw_lens(dist, n_len, m_len)
+    dist = _f32c(dist)
+    B, N, M = dist.shape
+    dev = dist.device
+    if N < 1 or M < 1:
+        raise ValueError(f"dist must have at least one row and one column; got {tuple(dist.shape)}")
+    R = torch.empty((B, N + 1, M + 1), device=dev)
+    total = torch.empty(B, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().hmm355_softdtw_f32(nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, float(gamma),
+                                               nat.ptr(R), nat.ptr(total), nat.stream_of(dev)))
+    return R, total
+
+
+@soft_dtw.register_fake
+def _(dist, gamma, n_len=None, m_len=None):
+    B, N, M = dist.shape
+    return dist.new_empty((B, N + 1, M + 1), dtype=torch.float32), dist.new_empty(B, dtype=torch.float32)
+
+
+@torch.library.custom_op("hmm355::soft_dtw_grad", mutates_args=())
+def soft_dtw_grad(dist: Tensor, R: Tensor, gamma: float, n_len: Optional[Tensor] = None,
+                  m_len: Optional[Tensor] = None) -> Tensor:
+    """E (B,N,M) = d total / d dist from dist and the R soft_dtw returned (hmm355_softdtw_grad_f32)."""
+    n_len, m_len = _dtw_lens(dist, n_len, m_len)
+    nat.require_gpu(R)
+    dist, R = _f32c(dist), _f32c(R)
+    B, N, M = dist.shape
+    if tuple(R.shape) != (B, N + 1, M + 1):
+        raise ValueError(f"R must be ({B}, {N + 1}, {M + 1}); got {tuple(R.shape)}")
+    dev = dist.device
+    E = torch.empty((B, N, M), device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().hmm355_softdtw_grad_f32(nat.ptr(dist), nat.ptr(R), nat.ptr(n_len), nat.ptr(m_len), B, N, M,
+                                                    float(gamma), nat.ptr(E), nat.stream_of(dev)))
+    return E
+
+
+@soft_dtw_grad.register_fake
+def _(dist, R, gamma, n_len=None, m_len=None):
+    return dist.new_empty(tuple(dist.shape), dtype=torch.float32)
