@@ -82,7 +82,7 @@ static __global__ void __launch_bounds__(kPrepThreads) band_prep_kernel(const fl
   __shared__ int dense_s;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   constexpr int NWV = kPrepThreads / 64;
-  if (kAbl & 16) return;  // diagnostic builds only (tools/ablate.py)
+  if (kAbl & abl::kNoPrep) return;  // diagnostic builds only (tools/ablate.py)
   for (int j = tid; j < kBandN; j += kPrepThreads) { clo_s[j] = rlo_s[j] = 1 << 20; chi_s[j] = rhi_s[j] = -1; }
   if (tid == 0) { red[0] = red[1] = 0; red[2] = red[4] = 1 << 20; red[3] = red[5] = -(1 << 20); dense_s = 0; }
   __syncthreads();
@@ -132,7 +132,7 @@ static __global__ void __launch_bounds__(kPrepThreads) band_prep_kernel(const fl
     }
   }
   __syncthreads();
-  if (kAbl & 8) return;
+  if (kAbl & abl::kPrepScanOnly) return;
   {
     // window widths and Toeplitz offset ranges: wave reductions, then one LDS atomic per wave
     int wcm = 0, wrm = 0, c0 = 1 << 20, c1 = -(1 << 20), r0 = 1 << 20, r1 = -(1 << 20);

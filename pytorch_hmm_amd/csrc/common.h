@@ -10,7 +10,8 @@
 
 #define HMM355_API extern "C" __attribute__((visibility("default")))
 
-// Ablation knobs for diagnostic builds only (tools/ablate.py); 0 in the product build.
+// Ablation knobs for diagnostic builds only (tools/ablate.py); 0 in the product build.  The bits
+// are named in namespace abl below.
 #ifndef HMM355_ABL
 #define HMM355_ABL 0
 #endif
@@ -19,9 +20,8 @@
 #define HMM355_STAMP 0
 #endif
 
-// Ablation knobs of the work beside the chains (csrc/follow.h), diagnostic builds only: 1 no
-// per-block publishing (completion only), 2 followers return at once (timing only), 4 plain
-// instead of write-through row / psi stores (timing only), 8 no log leaders.
+// HMM355_FABL: ablation knobs of the work beside the chains (csrc/follow.h), diagnostic builds
+// only; the bits are named in namespace fabl below.
 #ifndef HMM355_FBR
 #define HMM355_FBR 4  // posterior rows per follower wave per pass (follow.h)
 #endif
@@ -50,6 +50,43 @@ template <typename T>
 __device__ __forceinline__ void keep(T& v) { asm volatile("" : "+v"(v)); }
 constexpr int kAbl = HMM355_ABL;
 constexpr int kFAbl = HMM355_FABL;
+
+// The bits of HMM355_ABL: one meaning each, tested as `kAbl & abl::kName`.  Every one of them
+// gives wrong results: timing only.  The values 1, 2, 4, 8, 16 (tools/ablate.py) and 1, 1 << 20,
+// 1 << 21 (tools/ablate_hsmm.py) are passed by number: keep them.  Free: bits 8..13 and 27.
+namespace abl {
+constexpr int kNoStepBarrier = 1;           // step_barrier(): rec_run_dpp / rec_run_rb, hsmm.hip, semimarkov.hip
+constexpr int kDppNoProducts = 2;           // rec_run_dpp (NP = 256 only): sums / maxima of the inputs, no matrix
+constexpr int kDppNoBlockWork = 4;          // rec_run_dpp (NP = 256 only): no staging, loads or flushes
+constexpr int kPrepScanOnly = 8;            // band.h: the plan kernel stops after the matrix scan
+constexpr int kNoPrep = 16;                 // band.h: the plan kernel returns at once
+constexpr int kBandNoFlush = 32;            // rec_band helpers: no log-scale scan, no row flush
+constexpr int kBandNoStage = 64;            // rec_band helpers: no emission staging, no loads
+constexpr int kNoPsiRows = 128;             // rec_band, fused Viterbi: the psi waves compute nothing
+constexpr int kBandNoBlockBarrier = 1 << 14;  // band_chain / rec_band: no barrier per 16-step block
+constexpr int kBandNoHelperWork = 1 << 15;  // rec_band helpers: no block work at all
+constexpr int kFbAlphaOnly = 1 << 16;       // fb_kern.h: the beta workgroups return at once
+constexpr int kFbBetaOnly = 1 << 17;        // fb_kern.h: the alpha workgroups return at once
+constexpr int kPostPlainStores = 1 << 18;   // post.h: plain instead of non-temporal output stores
+constexpr int kHsmmForwardOnly = 1 << 19;   // hsmm.hip: no backtrace launches
+constexpr int kHsmmNoPred = 1 << 20;        // hsmm.hip: no predecessor scores
+constexpr int kHsmmNoSlots = 1 << 21;       // hsmm.hip: no slot work
+constexpr int kStageNoLog = 1 << 22;        // rec_stage: OBS_PROB Viterbi staging takes no log
+constexpr int kBandNoReduce = 1 << 23;      // band_chain: lane 0's value instead of the wave reduction
+constexpr int kBandReducePrev = 1 << 24;    // band_chain, Viterbi: the previous step's reduction (off the chain)
+constexpr int kPairNoScale = 1 << 25;       // fbpair.h: posteriors without the 1/s scaling
+constexpr int kPairNoTasks = 1 << 26;       // fbpair.h: no row tasks
+constexpr int kPairNoPostStores = 1 << 28;  // fbpair.h: no posterior stores
+constexpr int kPairNoStores = 1 << 29;      // fbpair.h: no output, scratch or posterior stores
+constexpr int kPairPlainStores = 1 << 30;   // fbpair.h: default cache policy instead of non-temporal
+}  // namespace abl
+// The bits of HMM355_FABL (`kFAbl & fabl::kName`); 2 and 4 are timing only.
+namespace fabl {
+constexpr int kNoBlockPublish = 1;  // rec_band: completion is published, the per-block counts are not
+constexpr int kNoFollowers = 2;     // follow.h: followers and log leaders return at once
+constexpr int kPlainStores = 4;     // rec_flush / psi copies: plain instead of write-through (sc1) stores
+constexpr int kNoLogLeaders = 8;    // follow.h: the log leaders return at once
+}  // namespace fabl
 
 // compile-time loop: f(integral_constant<int, J>) for J in [B, E)
 template <int J, int E, typename F>
@@ -207,9 +244,9 @@ __device__ __forceinline__ float log_obs_cr(float x) {
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-// the per-time-step barrier of the recursions (ablation bit 1 drops it: timing only)
+// the per-time-step barrier of the recursions (abl::kNoStepBarrier drops it: timing only)
 __device__ __forceinline__ void step_barrier() {
-  if constexpr (kAbl & 1)
+  if constexpr (kAbl & abl::kNoStepBarrier)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   else
     lds_barrier();

@@ -20,9 +20,9 @@ __global__ void __launch_bounds__(kFbNT<NP>) fb_recur_kernel(RecArgs fa, RecArgs
   }
   const int b = blockIdx.x >> 1;
   if (blockIdx.x & 1) {
-    if (!(kAbl & (1 << 20))) rec_dispatch<NP, kFbBeta>(fb, lds, b);  // diagnostic: alpha only
+    if (!(kAbl & abl::kFbAlphaOnly)) rec_dispatch<NP, kFbBeta>(fb, lds, b);  // diagnostic: alpha only
   } else {
-    if (!(kAbl & (1 << 21))) rec_dispatch<NP, kFbAlpha>(fa, lds, b);  // diagnostic: beta only
+    if (!(kAbl & abl::kFbBetaOnly)) rec_dispatch<NP, kFbAlpha>(fa, lds, b);  // diagnostic: beta only
   }
 }
 

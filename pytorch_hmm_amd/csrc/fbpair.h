@@ -53,7 +53,7 @@ struct PairArgs {
 // converts element-wise from a splat and loses the second dword)
 typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned int))));
 constexpr int kBufOOB = 0x7FFFFFF0;  // a byte offset past every num_records: store dropped, load 0
-constexpr int kBufNT = (kAbl & (1 << 30)) ? 0 : 2;  // gfx950 cache policy: non-temporal (diag 1 << 30: default)
+constexpr int kBufNT = (kAbl & abl::kPairPlainStores) ? 0 : 2;  // gfx950 cache policy: non-temporal (diagnostic builds: default)
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
 
   // ------------------------------------------------------------------------ helpers
   const int hi = w - 2;  // row tasks: helper hi owns the times t with t % NH == hi (both chains)
-  const bool tasks = !(kAbl & (1 << 26));  // (diagnostic bit 1 << 26: no row tasks, timing only)
+  const bool tasks = !(kAbl & abl::kPairNoTasks);  // (diagnostic builds: no row tasks, timing only)
   const size_t sb = (size_t)b * T;
   const unsigned slab_np = (unsigned)((size_t)T * NP * 4), slab_n = (unsigned)((size_t)T * N * 4);
   const __amdgpu_buffer_rsrc_t rU = buf_rsrc(p.fa.rows + sb * NP, slab_np);
@@ -325,7 +325,7 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
     }
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
-      if (kAbl & (1 << 29)) continue;  // (diag: no output / scratch stores)
+      if (kAbl & abl::kPairNoStores) continue;  // (diag: no output / scratch stores)
       buf_store<K, 0>(rS, soff[q], x[q]);
       if (full) {
         buf_store<K, kBufNT>(rO, ooff[q], o[q]);
@@ -347,8 +347,8 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
       const float sw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ps[q]), 63));
       const float is = sw > 0.f ? __builtin_amdgcn_rcpf(sw) : 0.f;
 #pragma unroll
-      for (int kk = 0; kk < K; ++kk) pp[q][kk] *= (kAbl & (1 << 25)) ? 1.f : is;
-      if (kAbl & ((1 << 28) | (1 << 29))) continue;  // (diag: no posterior stores)
+      for (int kk = 0; kk < K; ++kk) pp[q][kk] *= (kAbl & abl::kPairNoScale) ? 1.f : is;
+      if (kAbl & (abl::kPairNoPostStores | abl::kPairNoStores)) continue;  // (diag: no posterior stores)
       if (full) {
         buf_store<K, kBufNT>(rP, poff[q], pp[q]);
       } else {

@@ -73,7 +73,7 @@ __device__ __forceinline__ void follow_poll(const int* p, int need, int* slot, u
 template <int NP>
 __device__ __forceinline__ void vit_lead(const RecArgs& a, int b) {
   const int T = a.T, N = a.N, nblocks = (T + 15) / 16;
-  if (!a.lobuf || nblocks <= 4 || (kFAbl & (2 | 8))) return;
+  if (!a.lobuf || nblocks <= 4 || (kFAbl & (fabl::kNoFollowers | fabl::kNoLogLeaders))) return;
   const int tid = threadIdx.x, nt = blockDim.x;
   const size_t off = (size_t)b * T * N;
   const float* src = a.obs + off;
@@ -139,7 +139,7 @@ __device__ __forceinline__ void vit_decode_follow(const RecArgs& a, int b, float
     if (tid == 0 && a.final_score) a.final_score[b] = __builtin_bit_cast(float, 0x7fc00000u);
   };
   fstamp(0);
-  if (kFAbl & 2) return;
+  if (kFAbl & fabl::kNoFollowers) return;
   if (rec_band_code<kVit, NP>(a) == 0) {
     invalid();
     return;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void fb_post_follow(const RecArgs& fa, const RecArgs&
     if (tid == 0 && fa.lik_ref) fa.lik_ref[b] = __builtin_bit_cast(float, 0x7fc00000u);
   };
   fstamp(0);
-  if (kFAbl & 2) return;
+  if (kFAbl & fabl::kNoFollowers) return;
   if (rec_band_code<kFbAlpha, NP>(fa) == 0 || rec_band_code<kFbBeta, NP>(fb) == 0) {
     invalid();  // (the dense chains publish nothing: a plan passed as banded that is not)
     return;

@@ -269,7 +269,7 @@ __global__ void __launch_bounds__((HsG<SUB, NJ, SMAX>::NT)) hsmm_fwd_kernel(HsAr
         mid2();
         __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (kAbl & (1 << 21)) {  // ablation: no slot work (timing only)
+      if constexpr (kAbl & abl::kHsmmNoSlots) {  // ablation: no slot work (timing only)
         vv[p] = vv[p + NP2] = x;
         mx = fmaxf(mx, x);
         return;
@@ -327,7 +327,7 @@ __global__ void __launch_bounds__((HsG<SUB, NJ, SMAX>::NT)) hsmm_fwd_kernel(HsAr
     // M[t-1][s] = max_{s' != s} fl(Dm[t-1][s'] + logT[s'][s]) (the first s' attaining it is
     // recovered by the backtrace from the stored Dm row, for the path's segments only)
     lm = -INFINITY;
-    if constexpr (kAbl & (1 << 20)) {  // ablation: no predecessor scores (timing only)
+    if constexpr (kAbl & abl::kHsmmNoPred) {  // ablation: no predecessor scores (timing only)
       lm = lt2[0][0];
       return;
     }
@@ -350,7 +350,7 @@ __global__ void __launch_bounds__((HsG<SUB, NJ, SMAX>::NT)) hsmm_fwd_kernel(HsAr
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dmt), dg_r, st_off, t * S * 4, 0);
   };
   auto read_dq = [&](const int t, float4 (&dq)[NPRED / 4]) {
-    if constexpr (kAbl & (1 << 20)) return;
+    if constexpr (kAbl & abl::kHsmmNoPred) return;
     const float4* dp = reinterpret_cast<const float4*>(&L.dmx[(t - 1) & 1][sub * NPRED]);
 #pragma unroll
     for (int i = 0; i < NPRED / 4; ++i) dq[i] = dp[i];
@@ -970,7 +970,7 @@ static hipError_t launch_hsmm(const HsArgs& ha, const HsChunks& hc, unsigned fla
   hipLaunchKernelGGL((hsmm_fwd_kernel<SUB, NJ, SMAX>), dim3(ha.B), dim3(G::NT), lds, st, ha);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if constexpr (kAbl & (1 << 22)) return hipSuccess;  // ablation: forward only (timing)
+  if constexpr (kAbl & abl::kHsmmForwardOnly) return hipSuccess;  // ablation: forward only (timing)
   const size_t blds = hsmm_walk_lds(ha.S, ha.Dm, G::R);
   if (hsmm_use_chunks(ha.T, flags)) {
     const size_t wlds = align16(blds) + kHsCap * sizeof(int4);

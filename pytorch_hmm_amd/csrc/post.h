@@ -93,11 +93,11 @@ __global__ void __launch_bounds__(256) fb_posterior_kernel(PostArgs a) {
     if (vec) {
       VecK t;
       const size_t off = row * NP;
-      // outputs are not re-read here: non-temporal stores (kAbl bit 1 << 18 for plain ones)
+      // outputs are not re-read here: non-temporal stores (abl::kPostPlainStores for plain ones)
       auto put = [&](float* dst, const float (&x)[K]) {
         __builtin_memcpy(&t, x, sizeof(t));
         VecK* pd = reinterpret_cast<VecK*>(dst + off) + l;
-        if constexpr (kAbl & (1 << 18)) {
+        if constexpr (kAbl & abl::kPostPlainStores) {
           *pd = t;
         } else {
           typedef float nvec __attribute__((ext_vector_type(K)));

@@ -409,8 +409,8 @@ __device__ __forceinline__ void rec_stage(const RecArgs& a, float* lds, int blk,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const bool ok = qok && col + k < a.N;
-      // (diagnostic ablation bit 1 << 22: no log, timing only)
-      const float lv = (kAbl & (1 << 22)) ? r[k] + 1e-8f : logcr_fast(r[k] + 1e-8f, lt);
+      // (diagnostic builds: no log, timing only)
+      const float lv = (kAbl & abl::kStageNoLog) ? r[k] + 1e-8f : logcr_fast(r[k] + 1e-8f, lt);
       e[k] = KIND == kVit ? (ok ? lv : -INFINITY) : (ok ? r[k] + 1e-8f : 0.f);
     }
   }
@@ -472,7 +472,7 @@ __device__ __forceinline__ void rec_flush(const RecArgs& a, const float* lds, in
     const float4 v = *reinterpret_cast<const float4*>(lds + C::OFF_RING + (q & (C::RING - 1)) * NP + c4);
     const size_t tr = (size_t)b * a.T + rec_tau<KIND>(q, a.T);
     if ((WHAT & 1) && q < a.T) {
-      if (a.pub && !(kFAbl & 4)) {
+      if (a.pub && !(kFAbl & fabl::kPlainStores)) {
         // followers read these rows in this launch: write-through (sc1) 16-B stores (follow.h)
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             a.rows + (size_t)b * a.T * NP, (short)0, (int)((size_t)a.T * NP * 4), 0x00020000);
@@ -507,15 +507,76 @@ __device__ __forceinline__ void rec_flush(const RecArgs& a, const float* lds, in
       float* dst = a.rows + ((size_t)b * a.T + rec_tau<KIND>(q, a.T)) * a.row_stride + col;
       const float v = lds[C::OFF_RING + (q & (C::RING - 1)) * NP + col];
       if ((WHAT & 1) && q < a.T) {
-        if (a.pub && !(kFAbl & 4)) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sc1)
+        if (a.pub && !(kFAbl & fabl::kPlainStores)) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sc1)
         else *dst = v;
       }
     }
   }
 }
 
+// ---- what the dense and banded chains share ------------------------------------------------
+
+// the staged emission of step rho, state idx (the 3-slot ring of 16-step blocks, rec_stage)
+template <int NP>
+__device__ __forceinline__ const float& rec_emis(const float* lds, int rho, int idx) {
+  return lds[RC<NP>::OFF_EMIS + (((rho >> 4) % 3) * 16 + (rho & 15)) * NP + idx];
+}
+
+// Row 0 of state s, whose staged emission of step 0 is e0 (read only where it is used):
+// alpha_0 = p0 * e_0, beta_{T-1} = binit or 1, delta_0 = init + lo_0; padded states take the
+// neutral element.
 template <int NP, int KIND>
-__device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
+__device__ __forceinline__ float rec_row0(const RecArgs& a, int b, int s, const float& e0) {
+  const int N = a.N;
+  const int ss = s < N ? s : 0;
+  if (KIND == kFbAlpha) return s < N ? __expf(a.init[ss]) * e0 : 0.f;  // alpha_0 = p0 * e_0
+  if (KIND == kFbBeta) return s < N ? (a.binit ? a.binit[(size_t)b * NP + s] : 1.f) : 0.f;  // beta_{T-1}
+  return s < N ? a.init[ss] + e0 : -INFINITY;                          // delta_0 = init + lo_0
+}
+
+// Diagnostic builds (kStamp): the cycles of a dense chain wave by step segment, and its record
+// in g_rec_stamps (layout above).  Every member does nothing in the product build.
+struct RecStamps {
+  unsigned long long acc[4] = {0, 0, 0, 0}, prev = 0, t0 = 0, steps = 0;
+  long long rt0 = 0;
+  __device__ __forceinline__ void begin() {
+    if (kStamp) { t0 = stamp(); prev = t0; rt0 = __builtin_amdgcn_s_memrealtime(); }
+  }
+  // the cycles since the last mark belong to segment k
+  __device__ __forceinline__ void mark(int k) {
+    if (kStamp) { const unsigned long long t = stamp(); acc[k] += t - prev; prev = t; }
+  }
+  // lane 0 writes the wave's record into slot `slot`
+  __device__ __forceinline__ void finish(unsigned slot) {
+    if (kStamp && (threadIdx.x & 63) == 0) {
+      const unsigned long long t1 = stamp();
+      const long long rt1 = __builtin_amdgcn_s_memrealtime();
+      unsigned long long* o8 = g_rec_stamps + ((size_t)slot % kStampWaves) * 8;
+      o8[0] = acc[0]; o8[1] = acc[1]; o8[2] = acc[2]; o8[3] = acc[3];
+      o8[4] = steps; o8[5] = t1 - t0; o8[6] = t1 - t0; o8[7] = (unsigned long long)(rt1 - rt0);
+    }
+  }
+};
+
+// c_{T-1}, the sum of the last row (the log-likelihood's last term), from each lane's share ys
+// of it: one wave forms it and leaves it where rec_loglik reads it
+template <int NP>
+__device__ __forceinline__ void rec_keep_c_last(float* lds, int T, float ys) {
+  const float cs = wave_sum_bcast(ys);
+  if ((threadIdx.x & 63) == 0) lds[RC<NP>::OFF_SC + 64 * ((T - 1) & (RC<NP>::RING - 1))] = cs;
+}
+// loglik = LS_{T-1} + log c_{T-1}, for the wave whose `base` has run through the last block
+template <int NP>
+__device__ __forceinline__ float rec_loglik(const float* lds, int T, double base) {
+  return (float)(base + (double)__logf(lds[RC<NP>::OFF_SC + 64 * ((T - 1) & (RC<NP>::RING - 1))]));
+}
+
+// ---------------------------------------------------------------------------------------
+// Dense chain, DPP-broadcast form (round 1; the layout of the header comment).  The product
+// instantiates it at NP = 256 only: there 16 waves leave 128 VGPRs a lane, too few for the
+// register-blocked slices of rec_run_rb, which serves NP <= 128 (rec_dispatch).
+template <int NP, int KIND>
+__device__ __forceinline__ void rec_run_dpp(const RecArgs& a, float* lds, int b) {
   using C = RC<NP>;
   constexpr bool FB = KIND != kVit;
   const int tid = threadIdx.x;
@@ -544,26 +605,19 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
   if (nblocks > 1) rec_load<NP, KIND>(a, b, 1, w, l, er1);
   lds_barrier();
 
-  auto emis = [&](int rho, int idx) { return lds[C::OFF_EMIS + (((rho >> 4) % 3) * 16 + (rho & 15)) * NP + idx]; };
+  auto emis = [&](int rho, int idx) -> const float& { return rec_emis<NP>(lds, rho, idx); };
   // row 0 partials: the whole value in group 0, the identity in groups 1..3
   {
-    float v0;
-    const int oo = o < N ? o : 0;
-    if (KIND == kFbAlpha) v0 = o < N ? __expf(a.init[oo]) * emis(0, o) : 0.f;  // alpha_0 = p0 * e_0
-    else if (KIND == kFbBeta) v0 = o < N ? (a.binit ? a.binit[(size_t)b * NP + o] : 1.f) : 0.f;  // beta_{T-1}
-    else v0 = o < N ? a.init[oo] + emis(0, o) : -INFINITY;                      // delta_0 = init + lo_0
+    const float v0 = rec_row0<NP, KIND>(a, b, o, emis(0, o));
     const float ident = FB ? 0.f : -INFINITY;
     if (r < 2) lds[C::OFF_PART + o * 2 + r] = r == 0 ? v0 : ident;
   }
   lds_barrier();
 
   double base = (KIND == kFbBeta && a.bscale) ? (double)a.bscale[b] : 0.0;
-  unsigned long long st_acc[4] = {0, 0, 0, 0}, st_prev = 0, st_t0 = 0, st_steps = 0;
-  long long rt0 = 0;
-  if (kStamp) { st_t0 = stamp(); st_prev = st_t0; rt0 = __builtin_amdgcn_s_memrealtime(); }
-  auto mark = [&](int k) {
-    if (kStamp) { const unsigned long long t = stamp(); st_acc[k] += t - st_prev; st_prev = t; }
-  };
+  RecStamps stamps;
+  stamps.begin();
+  auto mark = [&](int k) { stamps.mark(k); };
   // sum (FB) / max (Viterbi) of the four row-group partials of input 64*blk + lane
   auto gather = [&](int prv, float (&y)[C::NBLK]) {
 #pragma unroll
@@ -582,7 +636,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
   };
 
   auto run_block = [&](int kb, float(&ernext)[5], float(&erfree)[5]) {
-    if (!(kAbl & 4)) {
+    if (!(kAbl & abl::kDppNoBlockWork)) {
       // straight-line staging and loads (the tail stages a padding block and re-loads the
       // last one), as in the banded helpers: exact waitcnt counts
       rec_stage<NP, KIND>(a, lds, kb + 1, w, l, ernext);
@@ -625,7 +679,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
           const int blk = g >> 2, n0 = 4 * (g & 3);
-          if (kAbl & 2) {
+          if (kAbl & abl::kDppNoProducts) {
             if ((g & 3) == 0) a0 += y[blk];
           } else {
             switch (n0) {
@@ -670,7 +724,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
         float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
 #pragma unroll
         for (int blk = 0; blk < C::NBLK; ++blk) {
-          if (kAbl & 2) { m0 = fmaxf(m0, y[blk]); continue; }
+          if (kAbl & abl::kDppNoProducts) { m0 = fmaxf(m0, y[blk]); continue; }
           m0 = fmaxf(m0, fmaxf(row_bcast<0>(y[blk]) + M[blk][0], row_bcast<1>(y[blk]) + M[blk][1]));
           m1 = fmaxf(m1, fmaxf(row_bcast<2>(y[blk]) + M[blk][2], row_bcast<3>(y[blk]) + M[blk][3]));
           m2 = fmaxf(m2, fmaxf(row_bcast<4>(y[blk]) + M[blk][4], row_bcast<5>(y[blk]) + M[blk][5]));
@@ -687,7 +741,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
       }
       if (kStamp) { keep(part); mark(1); }
       if (l < 32) lds[C::OFF_PART + (cur * NP + o) * 2 + r] = part;
-      if (kStamp) { mark(2); ++st_steps; }
+      if (kStamp) { mark(2); ++stamps.steps; }
       step_barrier();
     }
   };
@@ -695,13 +749,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
     run_block(k, er1, er0);
     if (k + 1 < nblocks) run_block(k + 1, er0, er1);
   }
-  if (kStamp && (tid & 63) == 0) {
-    const unsigned long long t1 = stamp();
-    const long long rt1 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o8 = g_rec_stamps + ((size_t)(blockIdx.x * C::NW + w) % kStampWaves) * 8;
-    o8[0] = st_acc[0]; o8[1] = st_acc[1]; o8[2] = st_acc[2]; o8[3] = st_acc[3];
-    o8[4] = st_steps; o8[5] = t1 - st_t0; o8[6] = t1 - st_t0; o8[7] = (unsigned long long)(rt1 - rt0);
-  }
+  stamps.finish(blockIdx.x * C::NW + w);
   // final row T-1 (its partials were written by the last step, or are the init for T == 1)
   float y[C::NBLK];
   gather((T - 1) & 1, y);
@@ -710,8 +758,7 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
     float ys = y[0];
 #pragma unroll
     for (int blk = 1; blk < C::NBLK; ++blk) ys += y[blk];
-    const float cs = wave_sum_bcast(ys);
-    if (l == 0) lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))] = cs;  // c_{T-1} (loglik only)
+    rec_keep_c_last<NP>(lds, T, ys);  // (loglik only)
   }
   lds_barrier();
   if (nblocks >= 2)
@@ -719,189 +766,6 @@ __device__ __forceinline__ void rec_run(const RecArgs& a, float* lds, int b) {
   rec_flush<NP, KIND>(a, lds, b, nblocks - 1, tid, rec_ls_scan<NP, KIND>(a, lds, b, nblocks - 1, base, w == C::NW - 1));
   if (KIND == kFbAlpha && a.loglik && tid == C::NT - 64) {
     // loglik = LS_{T-1} + log c_{T-1}; `base` (wave NW-1) now holds LS_{T-1}
-    a.loglik[b] = (float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Dense chain, register-operand form (NP <= 128; round 2).  Same lane layout as rec_run
-// (wave w owns outputs 16w + c, the lane's row r owns inputs 64*blk + 16r + n), but the
-// previous vector is not broadcast by DPP: every lane reads its row's 16 inputs per block
-// from LDS (4 ds_read_b128 at one address per 16-lane row: broadcasts, conflict-free) and
-// the products run as packed fp32 (v_pk_fma_f32, two inputs per instruction; Viterbi
-// v_pk_add_f32 + v_max3).  rec_run's v_fmac_f32_dpp issues at half rate, so its compute
-// phase was ~680 cycles per step on the slower wave of each SIMD (tools/stamps.py); here
-// the same 16K products are 16 packed ops per wave.  The four row groups are summed in
-// registers (permlane32 + permlane16 swaps), so each step writes ONE value per output
-// (lanes 0..15): Y[2][NP] holds the rows, and for beta P[2][NP] its product input v * e.
-template <int NP, int KIND>
-__device__ __forceinline__ void rec_run_bc(const RecArgs& a, float* lds, int b) {
-  using C = RC<NP>;
-  static_assert(NP <= 128, "register-operand dense chain: NP <= 128");
-  constexpr bool FB = KIND != kVit;
-  constexpr int NBK = C::NBLK;
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const int tid = threadIdx.x;
-  const int w = tid >> 6, l = tid & 63, r = l >> 4, c = l & 15;
-  const int o = 16 * w + c;  // output of this lane
-  const int T = a.T, N = a.N;
-  float* Y = lds + C::OFF_PART;            // [2][NP] rows (alpha u, beta v, Viterbi delta)
-  float* Pv = lds + C::OFF_PART + 2 * NP;  // [2][NP] beta: product input v * e
-
-  // matrix slice as pairs: M2[blk][m] = (Mat[i][o], Mat[i+1][o]) (beta: Mat[o][i]),
-  // i = 64 blk + 16 r + 2 m
-  f2 M2[NBK][8];
-#pragma unroll
-  for (int blk = 0; blk < NBK; ++blk)
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      const int i = 64 * blk + 16 * r + n;
-      const bool ok = i < N && o < N;
-      const size_t idx = ok ? (KIND == kFbBeta ? (size_t)o * N + i : (size_t)i * N + o) : 0;
-      const float v = a.mat[idx];
-      M2[blk][n >> 1][n & 1] = FB ? __expf(ok ? v : -INFINITY) : (ok ? v : -INFINITY);
-    }
-
-  const int nblocks = (T + 15) / 16;
-  float er0[5], er1[5];
-  if (KIND == kVit) rec_logt_fill<NP>(lds, l);
-  rec_load<NP, KIND>(a, b, 0, w, l, er0);
-  rec_stage<NP, KIND>(a, lds, 0, w, l, er0);
-  if (nblocks > 1) rec_load<NP, KIND>(a, b, 1, w, l, er1);
-  lds_barrier();
-
-  auto emis = [&](int rho, int idx) { return lds[C::OFF_EMIS + (((rho >> 4) % 3) * 16 + (rho & 15)) * NP + idx]; };
-  {
-    float v0;
-    const int oo = o < N ? o : 0;
-    if (KIND == kFbAlpha) v0 = o < N ? __expf(a.init[oo]) * emis(0, o) : 0.f;  // alpha_0 = p0 * e_0
-    else if (KIND == kFbBeta) v0 = o < N ? (a.binit ? a.binit[(size_t)b * NP + o] : 1.f) : 0.f;  // beta_{T-1}
-    else v0 = o < N ? a.init[oo] + emis(0, o) : -INFINITY;                      // delta_0 = init + lo_0
-    if (l < 16) {
-      Y[o] = v0;
-      if (KIND == kFbBeta) Pv[o] = v0 * emis(0, o);
-    }
-  }
-  lds_barrier();
-
-  double base = (KIND == kFbBeta && a.bscale) ? (double)a.bscale[b] : 0.0;
-  unsigned long long st_acc[4] = {0, 0, 0, 0}, st_prev = 0, st_t0 = 0, st_steps = 0;
-  long long rt0 = 0;
-  if (kStamp) { st_t0 = stamp(); st_prev = st_t0; rt0 = __builtin_amdgcn_s_memrealtime(); }
-  auto mark = [&](int k) {
-    if (kStamp) { const unsigned long long t = stamp(); st_acc[k] += t - st_prev; st_prev = t; }
-  };
-  auto keep_row = [&](int rho, const float (&y)[NBK]) {
-    if (w == 0) {
-#pragma unroll
-      for (int blk = 0; blk < NBK; ++blk) lds[C::OFF_RING + (rho & (C::RING - 1)) * NP + 64 * blk + l] = y[blk];
-    }
-  };
-
-  auto run_block = [&](int kb, float(&ernext)[5], float(&erfree)[5]) {
-    rec_stage<NP, KIND>(a, lds, kb + 1, w, l, ernext);
-    rec_load<NP, KIND>(a, b, kb + 2 < nblocks ? kb + 2 : nblocks - 1, w, l, erfree);
-    if (kb >= 2) rec_flush<NP, KIND>(a, lds, b, kb - 2, tid, rec_ls_scan<NP, KIND>(a, lds, b, kb - 2, base, w == C::NW - 1));
-    const int q0 = kb * 16 < 1 ? 1 : kb * 16;
-    const int q1 = (kb + 1) * 16 < T ? (kb + 1) * 16 : T;
-    for (int q = q0; q < q1; ++q) {
-      const int prv = (q - 1) & 1, cur = q & 1;
-      const float eo = emis(q, o);  // alpha / Viterbi: emission of output o; beta: of v_q -> P
-      if (kStamp) mark(3);
-      const float* src = (KIND == kFbBeta ? Pv : Y) + prv * NP;
-      f2 yin[NBK][8];
-      float yown[NBK], cx = 0.f;
-#pragma unroll
-      for (int blk = 0; blk < NBK; ++blk) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float4 v4 = *reinterpret_cast<const float4*>(src + 64 * blk + 16 * r + 4 * k);
-          yin[blk][2 * k] = f2{v4.x, v4.y};
-          yin[blk][2 * k + 1] = f2{v4.z, v4.w};
-        }
-        yown[blk] = Y[prv * NP + 64 * blk + l];
-        if (FB) cx += src[64 * blk + l];  // the normaliser's input (beta: sum of v * e)
-      }
-      if (kStamp) { keep(yown[0]); mark(0); }
-      keep_row(q - 1, yown);
-      float h;
-      float cs = 0.f;
-      if (FB) {
-        f2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
-#pragma unroll
-        for (int blk = 0; blk < NBK; ++blk)
-#pragma unroll
-          for (int m = 0; m < 8; m += 2) {
-            acc0 = __builtin_elementwise_fma(yin[blk][m], M2[blk][m], acc0);
-            acc1 = __builtin_elementwise_fma(yin[blk][m + 1], M2[blk][m + 1], acc1);
-          }
-        cs = wave_sum_bcast(cx);  // c_{q-1}, beside the products
-        h = (acc0.x + acc0.y) + (acc1.x + acc1.y);
-      } else {
-        float m0 = -INFINITY, m1 = -INFINITY;
-#pragma unroll
-        for (int blk = 0; blk < NBK; ++blk)
-#pragma unroll
-          for (int m = 0; m < 8; m += 2) {
-            const f2 t0 = yin[blk][m] + M2[blk][m];
-            const f2 t1 = yin[blk][m + 1] + M2[blk][m + 1];
-            m0 = fmaxf(m0, fmaxf(t0.x, t0.y));
-            m1 = fmaxf(m1, fmaxf(t1.x, t1.y));
-          }
-        h = fmaxf(m0, m1);
-      }
-      // the four row groups: rows {0,2} / {1,3} (permlane32), then {0,1} (permlane16)
-      float h1 = h;
-      permlane32_swap(h, h1);
-      h = FB ? h + h1 : fmaxf(h, h1);
-      float h2 = h;
-      permlane16_swap(h, h2);
-      h = FB ? h + h2 : fmaxf(h, h2);
-      float val, pval = 0.f;
-      if (FB) {
-        const float scale = __builtin_amdgcn_rcpf(cs);
-        if (tid == 0) lds[C::OFF_SC + 64 * ((q - 1) & (C::RING - 1))] = cs;
-        val = KIND == kFbAlpha ? h * (scale * eo) : h * scale;  // alpha: u_q = z e_q / c;  beta: v_q = z / c
-        if (KIND == kFbBeta) pval = val * eo;
-      } else {
-        val = h + eo;  // delta_q = max(...) + lo_q (exact: monotone)
-      }
-      if (kStamp) { keep(val); mark(1); }
-      if (l < 16) {
-        Y[cur * NP + o] = val;
-        if (KIND == kFbBeta) Pv[cur * NP + o] = pval;
-      }
-      if (kStamp) { mark(2); ++st_steps; }
-      step_barrier();
-    }
-  };
-  for (int k = 0; k < nblocks; k += 2) {
-    run_block(k, er1, er0);
-    if (k + 1 < nblocks) run_block(k + 1, er0, er1);
-  }
-  if (kStamp && (tid & 63) == 0) {
-    const unsigned long long t1 = stamp();
-    const long long rt1 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o8 = g_rec_stamps + ((size_t)(blockIdx.x * C::NW + w) % kStampWaves) * 8;
-    o8[0] = st_acc[0]; o8[1] = st_acc[1]; o8[2] = st_acc[2]; o8[3] = st_acc[3];
-    o8[4] = st_steps; o8[5] = t1 - st_t0; o8[6] = t1 - st_t0; o8[7] = (unsigned long long)(rt1 - rt0);
-  }
-  float y[NBK];
-#pragma unroll
-  for (int blk = 0; blk < NBK; ++blk) y[blk] = Y[((T - 1) & 1) * NP + 64 * blk + l];
-  keep_row(T - 1, y);
-  if (KIND == kFbAlpha && a.loglik && w == C::NW - 1) {
-    float ys = y[0];
-#pragma unroll
-    for (int blk = 1; blk < NBK; ++blk) ys += y[blk];
-    const float cs = wave_sum_bcast(ys);
-    if (l == 0) lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))] = cs;  // c_{T-1} (loglik only)
-  }
-  lds_barrier();
-  if (nblocks >= 2)
-    rec_flush<NP, KIND>(a, lds, b, nblocks - 2, tid, rec_ls_scan<NP, KIND>(a, lds, b, nblocks - 2, base, w == C::NW - 1));
-  rec_flush<NP, KIND>(a, lds, b, nblocks - 1, tid, rec_ls_scan<NP, KIND>(a, lds, b, nblocks - 1, base, w == C::NW - 1));
-  if (KIND == kFbAlpha && a.loglik && tid == C::NT - 64) {
     a.loglik[b] = (float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
   }
 }
@@ -1029,10 +893,11 @@ __device__ __forceinline__ void rec_rb_helper(const RecArgs& a, float* lds, int 
 }
 
 // ---------------------------------------------------------------------------------------
-// Dense chain, register-blocked form (round 3; every NP).  rec_run_bc gives each lane ONE
-// output and 16 inputs per 64-block, so every step moves NP * NP * 4 bytes out of LDS
-// (64 KiB at NP = 128: 64 ds_read_b128 = 256 LDS-array cycles, the largest term of its
-// ~830-cycle step).  Here each lane owns FOUR outputs and NP/16 inputs, so the same products
+// Dense chain, register-blocked form (round 3; NP <= 128 in the product).  The round-2
+// register-operand form (removed) gave each lane ONE output and 16 inputs
+// per 64-block, so every step moved NP * NP * 4 bytes out of LDS (64 KiB at NP = 128:
+// 64 ds_read_b128 = 256 LDS-array cycles, the largest term of its ~830-cycle step).
+// Here each lane owns FOUR outputs and NP/16 inputs, so the same products
 // need a quarter of the LDS traffic (2 ds_read_b128 per lane at NP = 128):
 //   * wave w, row r (lane >> 4) owns output group g = 4w + r, i.e. outputs 4g .. 4g+3; lane
 //     c (lane & 15) of the row owns inputs 64m + 4c .. 64m + 4c + 3 (m < NP/64), read as one
@@ -1100,14 +965,10 @@ __device__ __forceinline__ void rec_run_rb(const RecArgs& a, float* lds, int b) 
   }
   lds_barrier();  // (block 1 on: the helpers stage)
 
-  auto emis = [&](int rho, int idx) { return lds[C::OFF_EMIS + (((rho >> 4) % 3) * 16 + (rho & 15)) * NP + idx]; };
+  auto emis = [&](int rho, int idx) -> const float& { return rec_emis<NP>(lds, rho, idx); };
   const bool writer = (c & 3) == 0;
   {
-    float v0;
-    const int oo = o < N ? o : 0;
-    if (KIND == kFbAlpha) v0 = o < N ? __expf(a.init[oo]) * emis(0, o) : 0.f;  // alpha_0 = p0 * e_0
-    else if (KIND == kFbBeta) v0 = o < N ? (a.binit ? a.binit[(size_t)b * NP + o] : 1.f) : 0.f;  // beta_{T-1}
-    else v0 = o < N ? a.init[oo] + emis(0, o) : -INFINITY;                      // delta_0 = init + lo_0
+    const float v0 = rec_row0<NP, KIND>(a, b, o, emis(0, o));
     if (writer) {
       ring[o] = v0;
       if (KIND == kFbBeta) Pv[o] = v0 * emis(0, o);
@@ -1115,12 +976,9 @@ __device__ __forceinline__ void rec_run_rb(const RecArgs& a, float* lds, int b) 
   }
   lds_barrier();
 
-  unsigned long long st_acc[4] = {0, 0, 0, 0}, st_prev = 0, st_t0 = 0, st_steps = 0;
-  long long rt0 = 0;
-  if (kStamp) { st_t0 = stamp(); st_prev = st_t0; rt0 = __builtin_amdgcn_s_memrealtime(); }
-  auto mark = [&](int k) {
-    if (kStamp) { const unsigned long long t = stamp(); st_acc[k] += t - st_prev; st_prev = t; }
-  };
+  RecStamps stamps;
+  stamps.begin();
+  auto mark = [&](int k) { stamps.mark(k); };
 
   // one step q of the chain (ring row q from row q - 1)
   auto stepq = [&](int q) {
@@ -1197,7 +1055,7 @@ __device__ __forceinline__ void rec_run_rb(const RecArgs& a, float* lds, int b) 
     // (tools/mb_dense.hip: 291 -> 268 ns per Viterbi step, 255 -> 229 ns FB)
     ring[(q & (C::RING - 1)) * NP + o] = val;
     if (KIND == kFbBeta) Pv[(q & 1) * NP + o] = pval;
-    if (kStamp) { mark(2); ++st_steps; }
+    if (kStamp) { mark(2); ++stamps.steps; }
     step_barrier();
   };
   auto run_block = [&](int kb) {
@@ -1215,19 +1073,12 @@ __device__ __forceinline__ void rec_run_rb(const RecArgs& a, float* lds, int b) 
     }
   };
   for (int k = 0; k < nblocks; ++k) run_block(k);
-  if (kStamp && (tid & 63) == 0) {
-    const unsigned long long t1 = stamp();
-    const long long rt1 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o8 = g_rec_stamps + ((size_t)(blockIdx.x * C::NW + w) % kStampWaves) * 8;
-    o8[0] = st_acc[0]; o8[1] = st_acc[1]; o8[2] = st_acc[2]; o8[3] = st_acc[3];
-    o8[4] = st_steps; o8[5] = t1 - st_t0; o8[6] = t1 - st_t0; o8[7] = (unsigned long long)(rt1 - rt0);
-  }
+  stamps.finish(blockIdx.x * C::NW + w);
   if (KIND == kFbAlpha && a.loglik && w == C::NW - 1) {
     float ys = 0.f;
 #pragma unroll
     for (int m = 0; m < NM; ++m) ys += ring[((T - 1) & (C::RING - 1)) * NP + 64 * m + l];
-    const float cs = wave_sum_bcast(ys);
-    if (l == 0) lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))] = cs;  // c_{T-1} (loglik only)
+    rec_keep_c_last<NP>(lds, T, ys);  // (loglik only)
   }
   lds_barrier();  // the last blocks' flush and the log-likelihood: the helpers
 }
@@ -1287,18 +1138,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     float e0[NB];
     ld(erow(0), e0);
 #pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int s = NB * l + j;
-      const int ss = s < N ? s : 0;
-      if (KIND == kFbAlpha) y[j] = s < N ? __expf(a.init[ss]) * e0[j] : 0.f;
-      else if (KIND == kFbBeta) y[j] = s < N ? (a.binit ? a.binit[(size_t)b * NP + s] : 1.f) : 0.f;
-      else y[j] = s < N ? a.init[ss] + e0[j] : -INFINITY;
-    }
+    for (int j = 0; j < NB; ++j) y[j] = rec_row0<NP, KIND>(a, b, NB * l + j, e0[j]);
   }
   float* ybuf = lds + C::OFF_PART;  // beta's LDS window source [2][NP] (LDS-window mode)
   constexpr int EL = KIND == kFbBeta ? 1 : 0;
   float en[NB];  // the next step's emission (alpha / Viterbi e_q, beta e_{q-1})
-  float gprev = -INFINITY;  // (diagnostic bit 1 << 24)
+  float gprev = -INFINITY;  // (abl::kBandReducePrev)
 
   // the value of state s + dd (s = NB*l + j) from register vector v
   auto at = [&](const float(&v)[NB], int j, int dd) -> float {
@@ -1337,7 +1182,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
 #pragma unroll
       for (int j = 0; j < NB; ++j) { src[j] = y[j] * eo[j]; t = j == 0 ? src[j] : t + src[j]; }
       if (TW == 0) st(ybuf + ((q - 1) & 1) * NP + NB * l, src);
-      cs = (kAbl & (1 << 23)) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diag 1 << 23: no reduction)
+      cs = (kAbl & abl::kBandNoReduce) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diagnostic builds: no reduction)
       // the floor term fl_j * c is folded into the end: y_j = fl_j + (window sum) / c, one fma
       // after the reduction instead of a multiply before the window fmas and one after
 #pragma unroll
@@ -1346,7 +1191,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       float t = 0.f;
 #pragma unroll
       for (int j = 0; j < NB; ++j) { src[j] = y[j]; t = j == 0 ? y[j] : t + y[j]; }
-      cs = (kAbl & (1 << 23)) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diag 1 << 23: no reduction)
+      cs = (kAbl & abl::kBandNoReduce) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diagnostic builds: no reduction)
       float sw;
       if constexpr (decltype(UA)::value) {
         sw = 0.f;  // uniform floor: folded into the end as for beta, y = (afl0 + wsum / c) e
@@ -1362,12 +1207,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       float g = -INFINITY;
 #pragma unroll
       for (int j = 0; j < NB; ++j) { src[j] = y[j]; g = fmaxf(g, y[j] + fl[j]); }
-      // (diagnostic timing bits, wrong results: 1 << 23 no reduction, 1 << 24 the reduction of
-      // the previous step's values, off the step's dependency chain)
+      // (diagnostic timing bits, wrong results: kBandNoReduce no reduction, kBandReducePrev the
+      // reduction of the previous step's values, off the step's dependency chain)
       float M;
-      if constexpr (kAbl & (1 << 23)) {
+      if constexpr (kAbl & abl::kBandNoReduce) {
         M = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g)));
-      } else if constexpr (kAbl & (1 << 24)) {
+      } else if constexpr (kAbl & abl::kBandReducePrev) {
         M = wave_max_bcast(gprev);
         gprev = g;
       } else {
@@ -1452,7 +1297,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       }
       unsigned long long sb = 0;
       if (kStamp) sb = stamp();
-      if (!(kAbl & 16384)) lds_barrier();  // B_{kb+1}: block kb+1 staged by the helpers, rows of block kb-1 written
+      if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();  // B_{kb+1}: block kb+1 staged by the helpers, rows of block kb-1 written
       if (kStamp) st_bar += stamp() - sb;
     }
   };
@@ -1475,8 +1320,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     float t = 0.f;
 #pragma unroll
     for (int j = 0; j < NB; ++j) t += y[j];
-    const float cs = wave_sum_bcast(t);
-    if (l == 0) lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))] = cs;
+    rec_keep_c_last<NP>(lds, T, t);
   }
   lds_barrier();
 }
@@ -1596,7 +1440,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
     }
     auto psi_rows = [&](int bk) {
       if constexpr (FUSE) {
-        if (bk < 0 || (kAbl & 128)) return;
+        if (bk < 0 || (kAbl & abl::kNoPsiRows)) return;
         constexpr int NPW = WIDE ? 6 : 3, PR = (16 + NPW - 1) / NPW;
         const int hw = grp;
 #pragma unroll
@@ -1682,7 +1526,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
         const u32x4_t v = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const uint8_t*>(lds + C::OFF_PSR) +
                                                             (t & (C::PSR - 1)) * NP + 16 * pc);
         if (bk >= 0 && hidx < 16 * PER && t < T)
-          __builtin_amdgcn_raw_buffer_store_b128(v, psi_rs, t * NP + 16 * pc, 0, (kFAbl & 4) ? 0 : kAuxSc1);
+          __builtin_amdgcn_raw_buffer_store_b128(v, psi_rs, t * NP + 16 * pc, 0, (kFAbl & fabl::kPlainStores) ? 0 : kAuxSc1);
       }
     };
     // Straight-line block work (no branch around the staging or the loads: the tail stages
@@ -1700,7 +1544,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
       const int kload = kb + 3 < nblocks ? kb + 3 : nblocks - 1;
       // the block's log-scales once per helper (its own base); helper 1 writes LA / LB
       float lsv = 0.f;
-      if (!(kAbl & 32) && kb >= 2) lsv = rec_ls_scan<NP, KIND>(a, lds, b, kb - 2, base, w == 1);
+      if (!(kAbl & abl::kBandNoFlush) && kb >= 2) lsv = rec_ls_scan<NP, KIND>(a, lds, b, kb - 2, base, w == 1);
       // Viterbi: the block's source -- the leaders' log rows when they are ready, else the raw
       // emissions (the staging takes the log)
       const bool fromlog = KIND == kVit && a.lobuf && kload >= 4 && lp >= kload + 1;
@@ -1709,32 +1553,32 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
 #pragma unroll
       for (int h = 0; h < HV; ++h) {
         const int vw = vw_of(h);
-        if (vw < C::NW && !(kAbl & 32768)) {
-          if (!(kAbl & 64)) {
+        if (vw < C::NW && !(kAbl & abl::kBandNoHelperWork)) {
+          if (!(kAbl & abl::kBandNoStage)) {
             rec_stage<NP, KIND, FUSE>(a, lds, kb + 1, vw, l, ernext[h]);
             rec_load<NP, KIND, decltype(FULLC)::value, FUSE>(a, b, kload, vw, l, erfree[h], src, vmode);
           }
-          if (!(kAbl & 32) && kb >= 2) rec_flush<NP, KIND>(a, lds, b, kb - 2, l + 64 * vw, lsv);
+          if (!(kAbl & abl::kBandNoFlush) && kb >= 2) rec_flush<NP, KIND>(a, lds, b, kb - 2, l + 64 * vw, lsv);
         }
       }
       psi_copy(kb - 3);
       if (KIND == kVit && a.lready) lp = poll_count(a.lready + b * kPubStride, a.token, nblocks);
       // every fourth block (Viterbi: whole 64-step chunks of psi rows), after this block's loads
       // (so the stores it signals are never waited for sooner than three blocks on)
-      if (pubon && !(kFAbl & 1) && hi == 0 && l == 0) {
+      if (pubon && !(kFAbl & fabl::kNoBlockPublish) && hi == 0 && l == 0) {
         const int cnt = FB ? kb - 5 : kb - 6;
         if (cnt > 0 && (cnt & 3) == 0) publish_count(pubp, cnt, a.token);
       }
       unsigned long long hs1 = 0;
       if (kStamp) { hs1 = stamp(); hs_work += hs1 - hs0; }
-      if (!(kAbl & 16384)) lds_barrier();
+      if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();
       if (kStamp) hs_wait += stamp() - hs1;
     };
     if constexpr (FUSE) {
       if (psiw) {  // psi-only waves: one compact loop, same barrier count as the helpers
         for (int kb = 0; kb < nblocks; ++kb) {
           psi_rows(kb - 2);
-          if (!(kAbl & 16384)) lds_barrier();
+          if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();
         }
         lds_barrier();  // the chain's last row
         psi_rows(nblocks - 2);
@@ -1798,7 +1642,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
           rec_flush<NP, KIND>(a, lds, b, nblocks - 1, l + 64 * vw, lsv1);
         }
         if (KIND == kFbAlpha && a.loglik && vw == C::NW - 1 && l == 0)
-          a.loglik[b] = (float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
+          a.loglik[b] = rec_loglik<NP>(lds, T, base);
       }
     }
     if constexpr (KIND == kFbAlpha) {
@@ -1877,17 +1721,14 @@ __device__ __forceinline__ void rec_dispatch(const RecArgs& a, float* lds, int b
     case 16 * 3 - 1 + 2: rec_band<NP, KIND, 2, -1, 3>(a, lds, b, a.band); break;
     case 16 * 3 + 0 + 2: rec_band<NP, KIND, 2, 0, 3>(a, lds, b, a.band); break;
     default:
-      // (diagnostic ablation bits: 1 << 25 the round-2 register-operand chain (NP <= 128),
-      // 1 << 24 the DPP-broadcast chain)
-      // (NP = 256 keeps the DPP-broadcast chain: 16 waves leave 128 VGPRs a lane, too few for
-      // the register-blocked slices)
-      if constexpr (NP <= 128 && !(kAbl & (3 << 24))) {
+      // dense: the register-blocked chain for NP <= 128; NP = 256 keeps the DPP-broadcast chain
+      // (16 waves leave 128 VGPRs a lane, too few for the register-blocked slices)
+      if constexpr (NP <= 128) {
         if (threadIdx.x >= kRbHelpers<NP>::NT) return;  // (waves beyond the chain and its helpers)
         rec_run_rb<NP, KIND>(a, lds, b);
       } else {
         if (threadIdx.x >= RC<NP>::NT) return;
-        if constexpr (NP <= 128 && !(kAbl & (1 << 24))) rec_run_bc<NP, KIND>(a, lds, b);
-        else rec_run<NP, KIND>(a, lds, b);
+        rec_run_dpp<NP, KIND>(a, lds, b);
       }
       break;
   }

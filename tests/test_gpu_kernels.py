@@ -81,8 +81,13 @@ def test_viterbi_hmmlayer_c1_params():
     assert np.array_equal(delta.cpu().numpy(), g["log_delta3"])
 
 
+# the chains' tails (one, two, three 16-step blocks; a short or a whole last block) and row 0, at
+# every padded width
+TAIL_NT = [(N, T) for N in (40, 100, 200) for T in (1, 2, 16, 17, 33)]
+
+
 @pytest.mark.parametrize("B,T,N", [(3, 1, 7), (2, 65, 64), (5, 129, 100), (1, 300, 256), (4, 64, 128),
-                                   (2, 257, 33)])
+                                   (2, 257, 33)] + [(2, T, N) for N, T in TAIL_NT])
 def test_viterbi_vs_c_oracle_shapes(B, T, N):
     """Ragged T around the 16-step staging blocks and 64-step chunks, N padded to 64/128/256."""
     rng = np.random.default_rng(B * 1000 + T * 7 + N)
@@ -131,6 +136,34 @@ def test_forward_backward_vs_fp64_oracle_shapes():
         post, _, _, loglik, _ = o.forward_backward(t(obs), t(lP), t(lp0), o.OBS_PROB, o.FB_POSTERIOR)
         np.testing.assert_allclose(post.cpu().numpy(), post64, atol=2e-5)
         np.testing.assert_allclose(loglik.cpu().numpy(), ll64, rtol=2e-6)
+
+
+@pytest.mark.parametrize("N,T,mode", [(N, T, "prob") for N, T in TAIL_NT] +
+                         [(N, 33, "log") for N in (40, 100, 200)])
+def test_forward_backward_tails_vs_fp64_oracle(N, T, mode):
+    """The dense chains' row 0 and tails (T of one, two and three 16-step blocks, a short or a
+    whole last block) at every padded width, all outputs: posterior atol 2e-5, loglik rtol 2e-6,
+    forward / backward rtol 1e-4 where the fp64 value is representable."""
+    B = 2
+    rng = np.random.default_rng(T * N)
+    obs = rng.random((B, T, N), dtype=np.float32)
+    P = rng.random((N, N), dtype=np.float32)
+    lP, lp0 = O.hmm_params(torch.from_numpy(P))
+    o = ops()
+    if mode == "log":
+        x = np.log((obs + np.float32(1e-8)).astype(np.float64)).astype(np.float32)
+        lo, obs_mode = x, o.OBS_LOG
+    else:
+        x, lo, obs_mode = obs, np.log(obs + np.float32(1e-8)), o.OBS_PROB
+    la, lb, post64, ll64 = O.c_fb64(lo, lP.numpy(), lp0.numpy())
+    post, fwd, bwd, loglik, _ = o.forward_backward(t(x), t(lP), t(lp0), obs_mode,
+                                                   o.FB_POSTERIOR | o.FB_FORWARD | o.FB_BACKWARD)
+    np.testing.assert_allclose(post.cpu().numpy(), post64, atol=2e-5)
+    np.testing.assert_allclose(loglik.cpu().numpy(), ll64, rtol=2e-6)
+    for ours, ref in ((fwd.cpu().numpy(), np.exp(la)), (bwd.cpu().numpy(), np.exp(lb))):
+        big = ref > 1e-30
+        np.testing.assert_allclose(ours[big], ref[big], rtol=1e-4)
+        assert np.all(np.abs(ours[~big]) < 1e-29)
 
 
 # ------------------------------------------------------------------------- mixture

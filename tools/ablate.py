@@ -1,12 +1,21 @@
-"""Diagnostic: time the recursion kernels of ablation builds (HMM355_ABL bits) in ONE
-process, interleaved rounds (cdna guide §5.4 rule 24).  Build: python tools/ablate.py build
-Run on the GPU box: python tools/ablate.py run"""
+"""Diagnostic: time the recursion kernels of ablation builds (HMM355_ABL bits, named in
+csrc/common.h namespace abl) in ONE process, interleaved rounds (cdna guide §5.4 rule 24).
+Build: python tools/ablate.py build      Run on the GPU box: python tools/ablate.py run
+
+What the default variants 0,1,2,31 change, by shape (env B, T, N; MAT=l2r for the banded chains):
+  1        no per-step barrier: the dense chains at every N (the default N = 128 included)
+  2        no products: only the DPP-broadcast dense chain, which serves 128 < N <= 256 -- run
+           with N=200; at N <= 128 the build equals variant 0
+  31       1 | 2 | 4 | 8 | 16: at N <= 128 it differs from variant 1 by the plan kernel alone
+           (8, 16: no band is found, so MAT=l2r takes the dense chains too); bits 2 and 4 again
+           need 128 < N <= 256
+The banded chains' bits (32, 64, 128, 1 << 14, 1 << 15, 1 << 23, 1 << 24) apply with MAT=l2r;
+pass them through ABL_VARIANTS."""
 import ctypes, os, sys, json
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 VARIANTS = [int(v) for v in os.environ.get("ABL_VARIANTS", "0,1,2,31").split(",")]
-LIBD = os.path.join(ROOT, "gpurun_out", "..", "tools", "ablate_libs")
 
 def libpath(v):
     return os.path.join(HERE, "ablate_libs", f"libhmm355_abl{v}.so")
@@ -19,7 +28,6 @@ if sys.argv[1] == "build":
     sys.exit(0)
 
 import torch
-import pytorch_hmm_amd._native as nat
 dev = torch.device("cuda", 0)
 B, T, N = int(os.environ.get("B", 32)), int(os.environ.get("T", 2000)), int(os.environ.get("N", 128))
 obs = torch.softmax(torch.randn(B, T, N, device=dev), -1)
@@ -32,7 +40,6 @@ lP = torch.log(P / P.sum(1, keepdim=True) + 1e-8); lp0 = torch.full((N,), -4.85,
 libs = {}
 for v in VARIANTS:
     L = ctypes.CDLL(libpath(v))
-    nat_L = nat.lib  # reuse argtypes by copying
     P_, I, U, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t
     L.hmm355_fb_workspace_bytes.argtypes, L.hmm355_fb_workspace_bytes.restype = [I, I, I], S
     L.hmm355_forward_backward_f32.argtypes = [P_, I, P_, P_, I, I, I, U, P_, P_, P_, P_, P_, P_, S, P_]

@@ -1,7 +1,9 @@
 """Diagnostic: per-segment cycles of one recursion step (HMM355_STAMP=1 build).
 Build here:  python tools/stamps.py build      Run on the GPU box: python tools/stamps.py
 Segments per step and wave: gather (barrier -> partials in VGPRs), compute (-> step result),
-write (ds_write issued + retired), barrier (+ loop overhead + the per-16-step staging)."""
+write (ds_write issued + retired), barrier (+ loop overhead + the per-16-step staging).
+The records are per translation unit and hmm355_debug_stamps_fb / _vit read those of the
+NP = 128 kernels: run with 64 < N <= 128 (any other N prints zeros)."""
 import ctypes, os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "ablate_libs", "libhmm355_stamp.so")
@@ -54,7 +56,8 @@ def report(tag, fn, nblocks):
     clk = a[:, 6] / np.maximum(a[:, 7], 1) * 100.0
     print(f"[{tag}] cycles/step by segment (mean over waves):",
           {k: round(float(seg[:, i].mean()), 1) for i, k in enumerate(names)},
-          "total/step", round(float((a[:, 5] / steps).mean()), 1), "clock MHz", round(float(np.median(clk)), 0))
+          "total/step", round(float((a[:, 5] / steps).mean()), 1), "clock MHz", round(float(np.median(clk)), 0),
+          "steps per wave", sorted({int(x) for x in a[:, 4]}))
     per_wave = seg.reshape(nblocks, NW, 4).mean(0)
     for w in range(NW):
         print(f"   wave {w}:", [round(float(x)) for x in per_wave[w]])
