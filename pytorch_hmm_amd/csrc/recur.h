@@ -75,25 +75,124 @@ struct kRbHelpers {
 template <int NP>
 constexpr int kFbNT = kRbHelpers<NP>::NT;
 
-// Sum over all 64 lanes with DPP only (row sums, then row_bcast:15 / row_bcast:31), read
-// from lane 63: wave-uniform.
-__device__ __forceinline__ float wave_sum_bcast(float x) {
-  x = row16_sum(x);
-  // row_bcast:15 / :31 folded into the add; rows outside the mask keep x (one instruction each)
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(x));
+// Level L (0..5) of the DPP reduction of a wave to lane 63: the four in-row levels (quad_perm x2,
+// row_ror:4, row_ror:8: every lane of a row holds the row's value), then row_bcast:15 and
+// row_bcast:31.  One v_add_f32_dpp / v_max_f32_dpp each, all of them the compiler's own
+// instructions, so its hazard recognizer pads a level only when fewer than two instructions
+// separate it from the write of its source (a DPP read of a VGPR a VALU just wrote: 2 wait
+// states), and no opaque asm block stands between the levels and the work around them.
+// The two row_bcast levels run with every row enabled and bound_ctrl: a row without a source
+// row (row 0; rows 0, 1) combines with 0 and holds a value nobody reads.  The result is taken
+// from lane 63 alone, and the lanes it descends from (lane 31 after row_bcast:15, lane 63)
+// always have a source: ((r3 + r2) + (r1 + r0)), as with the row masks 0xa / 0xc.
+template <bool MAX, int L>
+__device__ __forceinline__ float wave_red_level(float x) {
+  constexpr int CTRL = L == 0 ? 0xB1 : L == 1 ? 0x4E : L == 2 ? 0x124 : L == 3 ? 0x128 : L == 4 ? 0x142 : 0x143;
+  const float o = __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, L >= 4));
+  return MAX ? fmaxf(x, o) : x + o;
+}
+__device__ __forceinline__ float wave_lane63(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
 }
 
-// Max over all 64 lanes with DPP only, read from lane 63: wave-uniform.
+// Sum / max over all 64 lanes with DPP only, read from lane 63: wave-uniform.
+__device__ __forceinline__ float wave_sum_bcast(float x) {
+  static_for<0, 6>([&](auto L) { x = wave_red_level<false, decltype(L)::value>(x); });
+  return wave_lane63(x);
+}
 __device__ __forceinline__ float wave_max_bcast(float x) {
-  x = fmaxf(x, dpp_f<0xB1>(x));
-  x = fmaxf(x, dpp_f<0x4E>(x));
-  x = fmaxf(x, dpp_f<0x124>(x));
-  x = fmaxf(x, dpp_f<0x128>(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(x));
-  asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(x));
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+  static_for<0, 6>([&](auto L) { x = wave_red_level<true, decltype(L)::value>(x); });
+  return wave_lane63(x);
+}
+
+// The same reductions with filler work: a lone wave issues in order, so each of the six
+// dependent levels waits two issue slots for the one before it, v_readlane one for the last
+// level, and the first VALU read of the SGPR two for v_readlane.  fill(integral_constant<G>)
+// is called in gap G and issues instructions of the caller's that do not read the reduction:
+// G = 0..5 ahead of level G, 6 ahead of v_readlane, 7 behind it (kFillSlots slots each).
+// sched_barrier pins the fillers there: the scheduler does not model these hazards as latency
+// and leaves the later levels back to back, padded with s_nop.  (The empty asm ties each level
+// to its place among the barriers: the DPP intrinsics have no side effects, and instruction
+// selection otherwise emits a level behind the next gap's fillers.)  A gap left short is padded
+// by the compiler.  Same operations in the same order as the plain forms: identical bits.
+constexpr int kFillGaps = 8;
+constexpr int kFillSlots[kFillGaps] = {2, 2, 2, 2, 2, 2, 1, 2};
+// The fillers of gap G when the caller has NU of them: whole gaps first, the gap behind
+// v_readlane, then gaps 0, 1, 2 ... (a gap filled by half still costs its s_nop: of the
+// allocations measured -- in proportion to the slots, from the back, from the front -- this one
+// ran fastest); what exceeds all slots goes behind v_readlane too.
+constexpr int fill_cnt(int G, int NU) {
+  int rem = NU, all = 0;
+  for (int i = 0; i < kFillGaps; ++i) all += kFillSlots[i];
+  for (int i = 0; i < kFillGaps; ++i) {
+    const int g = i == 0 ? kFillGaps - 1 : i - 1;
+    const int c = kFillSlots[g] < rem ? kFillSlots[g] : rem;
+    if (g == G) return c + (G == kFillGaps - 1 && NU > all ? NU - all : 0);
+    rem -= c;
+  }
+  return 0;
+}
+// fillers [fill_lo(G), fill_lo(G + 1)) go to gap G: in the caller's order
+constexpr int fill_lo(int G, int NU) {
+  int lo = 0;
+  for (int g = 0; g < G; ++g) lo += fill_cnt(g, NU);
+  return lo;
+}
+__device__ __forceinline__ void fill_pin(float& x) { asm volatile("" : "+v"(x)); }
+template <bool MAX, typename F>
+__device__ __forceinline__ float wave_red_fill(float x, F&& fill) {
+  static_for<0, 6>([&](auto L) {
+    __builtin_amdgcn_sched_barrier(0);
+    fill(L);
+    __builtin_amdgcn_sched_barrier(0);
+    x = wave_red_level<MAX, decltype(L)::value>(x);
+    fill_pin(x);
+  });
+  __builtin_amdgcn_sched_barrier(0);
+  fill(std::integral_constant<int, 6>{});
+  __builtin_amdgcn_sched_barrier(0);
+  x = wave_lane63(x);
+  __builtin_amdgcn_sched_barrier(0);
+  fill(std::integral_constant<int, 7>{});
+  __builtin_amdgcn_sched_barrier(0);
+  return x;
+}
+
+// The banded FB step sums NB products p_j * e_j (the input of the normaliser's reduction) that
+// are also needed one by one.  Left to fp contraction (hipcc's default is fast) the backend
+// fuses ONE product of the first pair into an fma with the other, and which one depends on the
+// order the instructions reach it: any rescheduling of the step changed output bits.  So the
+// form is written out, with contraction off:
+//   prod_j = p_j * e_j for every j;  t = fma(p_a, e_a, prod_b);  t = fma(p_j, e_j, t), j = 2 ..
+// FIRST: (a, b) = (0, 1), else (1, 0) -- per instantiation what the compiler had chosen before
+// the form was pinned (band_chain: kSumFirst), so the bits stay what they were.
+template <int NB>
+__device__ __forceinline__ void prods(const float (&p)[NB], const float (&e)[NB], float (&prod)[NB]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < NB; ++j) prod[j] = p[j] * e[j];
+}
+template <int NB, bool FIRST>
+__device__ __forceinline__ float prod_sum(const float (&p)[NB], const float (&e)[NB], const float (&prod)[NB]) {
+#pragma clang fp contract(off)
+  if constexpr (NB == 1) {
+    return prod[0];
+  } else {
+    float t = FIRST ? fmaf(p[0], e[0], prod[1]) : fmaf(p[1], e[1], prod[0]);
+#pragma unroll
+    for (int j = 2; j < NB; ++j) t = fmaf(p[j], e[j], t);
+    return t;
+  }
+}
+// the same sum of finished values (no product in reach: across a loop's back edge)
+template <int NB>
+__device__ __forceinline__ float plain_sum(const float (&v)[NB]) {
+#pragma clang fp contract(off)
+  float t = v[0];
+#pragma unroll
+  for (int j = 1; j < NB; ++j) t = t + v[j];
+  return t;
 }
 
 // v_writelane_b32: lane LANE of dst takes the (wave-uniform) value v; the lane is an inline
@@ -1143,6 +1242,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   float* ybuf = lds + C::OFF_PART;  // beta's LDS window source [2][NP] (LDS-window mode)
   constexpr int EL = KIND == kFbBeta ? 1 : 0;
   float en[NB];  // the next step's emission (alpha / Viterbi e_q, beta e_{q-1})
+  // the step sum's pinned form (prod_sum): which product of the first pair is fused.  What the
+  // compiler chose per instantiation before the form was written out: the first one for four
+  // states per lane and for two with a Toeplitz window of offsets 0 .. +1 or 0 .. +2, else the
+  // second (read from the NP = 128 / 256 listings; LDS-window chains of NP = 128: the second)
+  constexpr bool kSumFirst = NB == 4 || (NB == 2 && TW >= 2 && TD0 >= 0);
+  float pp[NB], ee[NB];  // alpha: the factors of the row's products y_j = pp_j * ee_j, for the next step's sum
   float gprev = -INFINITY;  // (abl::kBandReducePrev)
 
   // the value of state s + dd (s = NB*l + j) from register vector v
@@ -1168,56 +1273,119 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // (fused Viterbi psi) goes into lane jj of `blk` by v_writelane, stored once per block
   // (lanes < 16, after the last step): no per-step address arithmetic or scalar-to-vector
   // moves on the chain.
-  auto step = [&](int q, int jj, bool last_in_block, auto UA, float* row, const float* enext, float& blk,
+  //
+  // A lone wave issues one instruction per ~4 cycles in order, and each of the six dependent
+  // DPP levels of the step's wave reduction may read its source only two issue slots after the
+  // level before wrote it.  Whatever the step holds that does not read the reduction (its
+  // `units`) is issued around it, where the slots would otherwise be s_nop pads: the row store
+  // and the next emission load, the window reads (LDS-window mode) and the window terms
+  // themselves -- FB: every fma into acc, the normaliser enters only in the closing fma; Viterbi:
+  // the adds v + w of the closing max.  (With per-row floors the alpha window sum starts from the
+  // second reduction, the weighted sum, so its fmas stay behind.)
+  // Units, in issue order (loads early, their consumers late):
+  //   0 the window source's store | the window reads | beta, LDS mode: the row store |
+  //   the emission load | the window terms
+  // beta and Viterbi pin them inside the reduction (wave_red_fill).  alpha issues them ahead of
+  // the plain reduction and leaves the placing to the compiler: pinned, its step measured slower
+  // under every allocation tried.
+  // (The v_writelane of the normaliser is an asm statement, which the hazard recognizer does not
+  // count as a slot: inside a gap it would be padded as if it were not there, so it stays behind
+  // v_readlane.)
+  // FP (alpha): the previous step ran in the same unrolled block, so its products are in reach
+  // of this step's sum; else the sum of the finished row
+  // RL (beta): the step's input row came across a loop's back edge -- every step of the rolled
+  // loop (the partial blocks) and step 0 of an unrolled block -- where the compiler had fused
+  // the first product whatever the window
+  auto step = [&](int q, int jj, bool last_in_block, auto UA, auto FP, auto RL, float* row, const float* enext, float& blk,
                   auto wlane) {
-    st(row + NB * l, y);  // row q-1: flushed by the helpers, window source in LDS mode
+    constexpr bool FILLED = KIND != kFbAlpha;
+    constexpr bool LW = TW == 0;                                     // LDS-window mode
+    constexpr bool WFILL = !(KIND == kFbAlpha && !decltype(UA)::value);  // the window terms are fillers
+    constexpr int NWIN = NB * WW;
+    constexpr int O_LD = 1, O_ST2 = O_LD + (LW ? NWIN : 0), O_EN = O_ST2 + (LW && KIND == kFbBeta ? 1 : 0);
+    constexpr int O_T = O_EN + 1, NU = O_T + (WFILL ? NWIN : 0);
     float eo[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) eo[j] = en[j];
-    if (!last_in_block) ld(enext, en);
-    float acc[NB], src[NB];
+    float acc[NB], src[NB], wl[NB][WW], tv[NB][WW];
     float cs = 0.f, scale = 1.f;
+    const float* wsrc = KIND == kFbBeta ? ybuf + ((q - 1) & 1) * NP : row;
+    // window term n: (k, j) in the order of the plain loops (k ascending for every j)
+    auto term = [&](int n) {
+      const int j = LW ? n / WW : n % NB, k = LW ? n % WW : n / NB;
+      float v;
+      if constexpr (LW) v = wl[j][k];
+      else v = at(src, j, TD0 + k);
+      if (FB) acc[j] = fmaf(v, wv[j][k], acc[j]);
+      else tv[j][k] = v + wv[j][k];
+    };
+    auto unit = [&](auto I) {
+      constexpr int i = decltype(I)::value;
+      if constexpr (i == 0) {
+        // row q-1: flushed by the helpers, window source in LDS mode (beta: the products)
+        if (LW && KIND == kFbBeta) st(ybuf + ((q - 1) & 1) * NP + NB * l, src);
+        else st(row + NB * l, y);
+      } else if constexpr (i < O_ST2) {
+        wl[(i - O_LD) / WW][(i - O_LD) % WW] = wsrc[lo[(i - O_LD) / WW] + (i - O_LD) % WW];
+      } else if constexpr (i < O_EN) {
+        st(row + NB * l, y);
+      } else if constexpr (i == O_EN) {
+        if (!last_in_block) ld(enext, en);
+      } else {
+        term(i - O_T);
+      }
+    };
+    auto fill = [&](auto G) { static_for<fill_lo(decltype(G)::value, NU), fill_lo(decltype(G)::value + 1, NU)>(unit); };
+    // (diagnostic timing bits, wrong results: kBandNoReduce no reduction, kBandReducePrev the
+    // reduction of the previous step's values, off the step's dependency chain)
+    auto reduce = [&](auto MAXOP, float t) -> float {
+      if constexpr (kAbl & abl::kBandNoReduce) {
+        static_for<0, NU>(unit);
+        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t)));
+      } else if constexpr (!FILLED) {
+        static_for<0, NU>(unit);
+        return decltype(MAXOP)::value ? wave_max_bcast(t) : wave_sum_bcast(t);
+      } else if constexpr (decltype(MAXOP)::value && (kAbl & abl::kBandReducePrev)) {
+        const float r = wave_red_fill<true>(gprev, fill);
+        gprev = t;
+        return r;
+      } else {
+        return wave_red_fill<decltype(MAXOP)::value>(t, fill);
+      }
+    };
     if (KIND == kFbBeta) {  // the product input is y = v * e_{q-1} (hmm.py:113-115)
-      float t = 0.f;
-#pragma unroll
-      for (int j = 0; j < NB; ++j) { src[j] = y[j] * eo[j]; t = j == 0 ? src[j] : t + src[j]; }
-      if (TW == 0) st(ybuf + ((q - 1) & 1) * NP + NB * l, src);
-      cs = (kAbl & abl::kBandNoReduce) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diagnostic builds: no reduction)
+      prods<NB>(y, eo, src);
+      const float t = prod_sum<NB, kSumFirst || decltype(RL)::value>(y, eo, src);
       // the floor term fl_j * c is folded into the end: y_j = fl_j + (window sum) / c, one fma
       // after the reduction instead of a multiply before the window fmas and one after
 #pragma unroll
       for (int j = 0; j < NB; ++j) acc[j] = 0.f;
+      cs = reduce(std::false_type{}, t);
     } else if (KIND == kFbAlpha) {
-      float t = 0.f;
 #pragma unroll
-      for (int j = 0; j < NB; ++j) { src[j] = y[j]; t = j == 0 ? y[j] : t + y[j]; }
-      cs = (kAbl & abl::kBandNoReduce) ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t))) : wave_sum_bcast(t);  // (diagnostic builds: no reduction)
-      float sw;
+      for (int j = 0; j < NB; ++j) src[j] = y[j];
+      float t;
+      if constexpr (decltype(FP)::value) t = prod_sum<NB, kSumFirst>(pp, ee, y);
+      else t = plain_sum<NB>(y);
       if constexpr (decltype(UA)::value) {
-        sw = 0.f;  // uniform floor: folded into the end as for beta, y = (afl0 + wsum / c) e
+        // uniform floor: folded into the end as for beta, y = (afl0 + wsum / c) e
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j] = 0.f;
+        cs = reduce(std::false_type{}, t);
       } else {
         float tw = 0.f;
 #pragma unroll
         for (int j = 0; j < NB; ++j) tw = fmaf(y[j], fl[j], tw);
-        sw = wave_sum_bcast(tw);
-      }
+        cs = reduce(std::false_type{}, t);
+        tw = wave_sum_bcast(tw);
 #pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = sw;
+        for (int j = 0; j < NB; ++j) acc[j] = tw;
+      }
     } else {
       float g = -INFINITY;
 #pragma unroll
       for (int j = 0; j < NB; ++j) { src[j] = y[j]; g = fmaxf(g, y[j] + fl[j]); }
-      // (diagnostic timing bits, wrong results: kBandNoReduce no reduction, kBandReducePrev the
-      // reduction of the previous step's values, off the step's dependency chain)
-      float M;
-      if constexpr (kAbl & abl::kBandNoReduce) {
-        M = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g)));
-      } else if constexpr (kAbl & abl::kBandReducePrev) {
-        M = wave_max_bcast(gprev);
-        gprev = g;
-      } else {
-        M = wave_max_bcast(g);
-      }
+      const float M = reduce(std::true_type{}, g);
       // fused psi: M_q = max_i fl(delta_{q-1,i} + r_i) is also psi row q's floor maximum
       if constexpr (FUSE) wlane(blk, M);
 #pragma unroll
@@ -1227,31 +1395,29 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       scale = __builtin_amdgcn_rcpf(cs);
       wlane(blk, cs);  // c_{q-1}
     }
-    if constexpr (TW > 0) {
+    if constexpr (!WFILL) {
+      static_for<0, NWIN>([&](auto I) { term(decltype(I)::value); });
+    } else if constexpr (!FB) {
 #pragma unroll
-      for (int k = 0; k < TW; ++k)
+      for (int n = 0; n < NWIN; ++n) {
+        const int j = LW ? n / WW : n % NB, k = LW ? n % WW : n / NB;
+        acc[j] = fmaxf(acc[j], tv[j][k]);
+      }
+    }
+    if constexpr (KIND == kFbAlpha) {
+      // y_j = pp_j * ee_j (padded states: the staged emission is 0)
 #pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const float v = at(src, j, TD0 + k);
-          acc[j] = FB ? fmaf(v, wv[j][k], acc[j]) : fmaxf(acc[j], v + wv[j][k]);
-        }
-    } else {
-      const float* wsrc = KIND == kFbBeta ? ybuf + ((q - 1) & 1) * NP : row;
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int k = 0; k < WW; ++k) {
-          const float v = wsrc[lo[j] + k];
-          acc[j] = FB ? fmaf(v, wv[j][k], acc[j]) : fmaxf(acc[j], v + wv[j][k]);
-        }
+      for (int j = 0; j < NB; ++j) {
+        if constexpr (decltype(UA)::value) { pp[j] = fmaf(acc[j], scale, afl0); ee[j] = eo[j]; }
+        else { pp[j] = acc[j]; ee[j] = scale * eo[j]; }
+      }
+      prods<NB>(pp, ee, y);
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       // padded states: the staged emission is 0 (FB) / -inf (Viterbi) and the floors 0
-      if (KIND == kFbAlpha) {
-        if constexpr (decltype(UA)::value) y[j] = fmaf(acc[j], scale, afl0) * eo[j];
-        else y[j] = acc[j] * (scale * eo[j]);
-      } else if (KIND == kFbBeta) {
+      if (KIND == kFbAlpha) continue;
+      if (KIND == kFbBeta) {
         y[j] = fmaf(acc[j], scale, fl[j]);
       } else {
         y[j] = acc[j] + eo[j];
@@ -1278,7 +1444,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       if (q0 == kb * 16 && q1 == kb * 16 + 16) {
         static_for<0, 16>([&](auto JJ) {
           constexpr int jj = decltype(JJ)::value;
-          step(kb * 16 + jj, jj, jj == 15, UA, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
+          step(kb * 16 + jj, jj, jj == 15, UA, std::bool_constant<(jj > 0)>{}, std::bool_constant<(jj == 0)>{}, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
                [](float& d, float v) { writelane_c<jj>(d, v); });
         });
         // the block's normalisers / floor maxima: lane jj -> row 16kb + jj - 1 (entry 0 of its
@@ -1291,7 +1457,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         for (int q = q0; q < q1; ++q) {
           const int jj = q - kb * 16;
           float* sc = lds + C::OFF_SC + 64 * ((q - 1) & (C::RING - 1));
-          step(q, jj, q + 1 == q1, UA, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
+          step(q, jj, q + 1 == q1, UA, std::false_type{}, std::true_type{}, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
                [sc](float&, float v) { *sc = v; });
         }
       }
