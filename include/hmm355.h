@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024]                  */
@@ -470,6 +470,60 @@ int hmm355_softdtw_f32(const float* dist, const int* n_len, const int* m_len, in
                        float gamma, float* R, float* total, void* stream);
 int hmm355_softdtw_grad_f32(const float* dist, const float* R, const int* n_len, const int* m_len,
                             int B, int N, int M, float gamma, float* E, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * CTC lattice (csrc/ctc.hip).  Replace the per-cell loops of ctc_forward_algorithm
+ * (alignment/ctc.py:32-121) and ctc_backward_algorithm (:124-199), and give ctc_alignment_path
+ * (:202-256) the alpha it never fills.  One launch per call, one workgroup per sequence and job
+ * (forward sum, backward sum, Viterbi).
+ *   log_probs (T,B,C) fp32 row-major; -inf entries are allowed, +inf and NaN are not
+ *   targets   (B,Lmax) int32; only the first target_lengths[b] of row b are read.  A label
+ *             outside [0, C) is never used as an index: its emission counts as -inf
+ *   input_lengths, target_lengths  (B) int32 device arrays.  The caller guarantees
+ *             1 <= input_lengths[b] <= T and 0 <= target_lengths[b] <= Lmax (the Python layer
+ *             checks them on the host); the kernels clamp what they read to those ranges
+ *   blank     in [0, C)
+ * Sequence b has S'_b = 2 target_lengths[b] + 1 positions, ext[s] = blank (s even) or
+ * targets[b, s / 2] (s odd); tables are (B,T,S') with S' = 2 Lmax + 1.
+ * T, B, C >= 1 (else HMM355_E_ARG); 1 <= Lmax <= HMM355_CTC_MAX_TARGET (else HMM355_E_STATES); a
+ * size that overflows returns HMM355_E_SHAPE; the size query returns 0 for any of them.
+ *
+ * hmm355_ctc_f32
+ *   loglik (B): LSE(alpha[T_b-1, S'_b-1], alpha[T_b-1, S'_b-2]) (the first alone when the target
+ *          is empty); -inf for a pair with no alignment.  Always produced.
+ *   flags  HMM355_CTC_ALPHA: store alpha (B,T,S'): alpha[0,0] = lp[0,b,blank], alpha[0,1] =
+ *            lp[0,b,ext[1]], then alpha[t,s] = lp[t,b,ext[s]] + LSE(alpha[t-1,s], alpha[t-1,s-1],
+ *            alpha[t-1,s-2] if ext[s] != ext[s-2]); frames >= input_lengths[b] and positions
+ *            >= S'_b are -inf.  Without it no (B,T,S') table is written for the forward sum.
+ *          HMM355_CTC_BETA: store beta (B,T,S') in the reference's convention, which leaves the
+ *            frame's own emission out: beta[T_b-1, S'_b-1] = beta[T_b-1, S'_b-2] = 0,
+ *            beta[t,s] = LSE over s' in {s, s+1, s+2 if ext[s] != ext[s+2]} of
+ *            beta[t+1,s'] + lp[t+1,b,ext[s']]; the same -inf fill.
+ *          HMM355_CTC_VITERBI: the best single path.  path (B,T) int32: the expanded position of
+ *            each frame, -1 for frames >= input_lengths[b] and in every frame of a pair with no
+ *            alignment; score (B): its log-probability (-inf then).  Ties go to the first of
+ *            s, s-1, s-2; the path ends in S'_b-1 unless S'_b-2 scores strictly higher.
+ *   workspace >= hmm355_ctc_workspace_bytes(B, T, Lmax, flags), 16-byte aligned (with
+ *          HMM355_CTC_VITERBI the 2-bit choices of every cell; 256 bytes otherwise).
+ * hmm355_ctc_grad_f32: from the alpha, beta and loglik of one hmm355_ctc_f32 call,
+ *   gamma (B,T,S') or NULL: exp(alpha + beta - loglik), 0 where either is -inf;
+ *   grad (T,B,C) = d loglik / d log_probs: grad[t,b,c] = sum of gamma[b,t,s] over ext[s] = c.
+ *   Both are 0 in frames >= input_lengths[b] and for a pair with no alignment.  No atomics: two
+ *   calls on the same inputs return the same bits.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_CTC_ALPHA 0x1u
+#define HMM355_CTC_BETA 0x2u
+#define HMM355_CTC_VITERBI 0x4u
+#define HMM355_CTC_MAX_TARGET 2048
+size_t hmm355_ctc_workspace_bytes(int B, int T, int Lmax, unsigned flags);
+int hmm355_ctc_f32(const float* log_probs, const int* targets, const int* input_lengths,
+                   const int* target_lengths, int T, int B, int C, int Lmax, int blank,
+                   unsigned flags, float* alpha, float* beta, float* loglik, int* path,
+                   float* score, void* workspace, size_t workspace_bytes, void* stream);
+int hmm355_ctc_grad_f32(const float* alpha, const float* beta, const float* loglik,
+                        const int* targets, const int* input_lengths, const int* target_lengths,
+                        int T, int B, int C, int Lmax, int blank, float* gamma, float* grad,
+                        void* stream);
 
 #ifdef __cplusplus
 }

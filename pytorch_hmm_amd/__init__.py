@@ -25,6 +25,6 @@ __all__ += ["HMMLayer", "GaussianHMMLayer", "MixtureGaussianHMMLayer", "HSMMLaye
             "StreamingHMMProcessor", "StreamingResult", "AdaptiveLatencyController"]
 
 from . import alignment
-from .alignment import ConstrainedDTWAligner, DTWAligner
+from .alignment import ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner
 
-__all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner"]
+__all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner", "CTCAligner", "CTCSegmentationAligner"]

@@ -27,6 +27,8 @@ NARROW_MAX_STATES = 256  # the chains of fb.hip / viterbi.hip (one workgroup per
 WIDE_MAX_STATES = 4096   # the batch-tiled *_wide entry points (csrc/wide.hip)
 DTW_SYMMETRIC, DTW_ASYMMETRIC, DTW_RABINER_JUANG = 0, 1, 2  # HMM355_DTW_* step patterns
 DTW_PATH = 0x1  # HMM355_DTW_PATH
+CTC_ALPHA, CTC_BETA, CTC_VITERBI = 0x1, 0x2, 0x4  # HMM355_CTC_* flags
+CTC_MAX_TARGET = 2048  # HMM355_CTC_MAX_TARGET
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -49,6 +51,7 @@ EXPORTS = (
     "hmm355_viterbi_wide_workspace_bytes", "hmm355_viterbi_wide_f32",
     "hmm355_fb_wide_workspace_bytes", "hmm355_forward_backward_wide_f32",
     "hmm355_dtw_workspace_bytes", "hmm355_dtw_f32", "hmm355_softdtw_f32", "hmm355_softdtw_grad_f32",
+    "hmm355_ctc_workspace_bytes", "hmm355_ctc_f32", "hmm355_ctc_grad_f32",
 )
 
 _lib = None
@@ -140,6 +143,9 @@ def lib():
     L.hmm355_dtw_f32.argtypes, L.hmm355_dtw_f32.restype = [P, P, P, I, I, I, I, U, P, P, P, P, P, P, S, P], I
     L.hmm355_softdtw_f32.argtypes, L.hmm355_softdtw_f32.restype = [P, P, P, I, I, I, F, P, P, P], I
     L.hmm355_softdtw_grad_f32.argtypes, L.hmm355_softdtw_grad_f32.restype = [P, P, P, P, I, I, I, F, P, P], I
+    L.hmm355_ctc_workspace_bytes.argtypes, L.hmm355_ctc_workspace_bytes.restype = [I, I, I, U], S
+    L.hmm355_ctc_f32.argtypes, L.hmm355_ctc_f32.restype = [P, P, P, P, I, I, I, I, I, U, P, P, P, P, P, P, S, P], I
+    L.hmm355_ctc_grad_f32.argtypes, L.hmm355_ctc_grad_f32.restype = [P, P, P, P, P, P, I, I, I, I, I, P, P, P], I
     _lib = L
     return L
 

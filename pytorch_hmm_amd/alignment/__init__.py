@@ -1,16 +1,31 @@
-"""pytorch_hmm_amd.alignment — drop-in for pytorch_hmm.alignment's dynamic time warping.
+"""pytorch_hmm_amd.alignment — drop-in for pytorch_hmm.alignment: dynamic time warping and CTC.
 
-compute_dtw_path, DTWAligner, ConstrainedDTWAligner, dtw_alignment, dtw_distance and
+DTW (dtw.py): compute_dtw_path, DTWAligner, ConstrainedDTWAligner, dtw_alignment, dtw_distance and
 phoneme_audio_alignment keep the reference's signatures and return conventions; their per-cell
 Python loops run as HIP kernels (csrc/dtw.hip: one workgroup per pair, one launch per call, a
 batch in one launch), and soft-DTW is differentiable through its own gradient kernel
-(autograd.SoftDTW).  The kernels take tensors on a ROCm GPU only.
+(autograd.SoftDTW).
 
-The reference's CTC alignment (pytorch_hmm.alignment.ctc) is out of scope here: CTCAligner wraps
-nn.CTCLoss, which already runs on the GPU, and ctc_alignment_path never fills its log_alpha.
+CTC (ctc.py): ctc_forward_algorithm and ctc_backward_algorithm, four-deep Python loops in the
+reference, are one launch of csrc/ctc.hip (one workgroup per sequence and direction);
+ctc_forward_algorithm is differentiable (autograd.CTCLogLik, the occupancy kernel).
+ctc_alignment_path and CTCAligner.align return by default what the reference returns -- all
+blank_id, because its alpha is never filled -- and with method="posterior" or "viterbi" the forced
+alignment it was written to give; ctc_forced_align also returns the expanded positions and the
+score.  CTCAligner.forward stays the reference's nn.CTCLoss wrapper; decoding, collapsing and
+CTCSegmentationAligner are plain torch on any device.
+
+The kernels take tensors on a ROCm GPU only.  Of the reference package's four listed techniques
+(DTW, CTC, attention, monotonic) it implements these two, and so does this package.
 """
+from .ctc import (CTCAligner, CTCSegmentationAligner, collapse_repeated_tokens, ctc_alignment_path,
+                  ctc_backward_algorithm, ctc_decode_sequence, ctc_forced_align, ctc_forward_algorithm,
+                  expand_targets_with_blank, remove_ctc_blanks)
 from .dtw import (ConstrainedDTWAligner, DTWAligner, compute_distance_matrix, compute_dtw_path, dtw_alignment,
                   dtw_distance, extract_phoneme_durations, phoneme_audio_alignment)
 
 __all__ = ["DTWAligner", "ConstrainedDTWAligner", "compute_distance_matrix", "compute_dtw_path", "dtw_alignment",
-           "dtw_distance", "phoneme_audio_alignment", "extract_phoneme_durations"]
+           "dtw_distance", "phoneme_audio_alignment", "extract_phoneme_durations",
+           "CTCAligner", "CTCSegmentationAligner", "ctc_forward_algorithm", "ctc_backward_algorithm",
+           "ctc_alignment_path", "ctc_forced_align", "expand_targets_with_blank", "remove_ctc_blanks",
+           "collapse_repeated_tokens", "ctc_decode_sequence"]

@@ -553,3 +553,39 @@ class SoftDTW(torch.autograd.Function):
         d, R = ctx.saved_tensors
         E = ops.soft_dtw_grad(d, R, ctx.gamma, *ctx.lens)
         return E * grad_total.to(E.dtype)[:, None, None], None, None, None
+
+
+class CTCLogLik(torch.autograd.Function):
+    """loglik (B) = the log-probability CTC gives the targets (ops.ctc, csrc/ctc.hip),
+    differentiable in log_probs (T,B,C).  The forward keeps alpha and beta; the backward is the
+    occupancy kernel (ops.ctc_grad): d loglik[b] / d log_probs[t,b,c] = the sum of
+    gamma[b,t,s] = exp(alpha + beta - loglik) over the positions s of class c, times grad_loglik.
+    Replaces autograd through the per-cell loop of ctc_forward_algorithm (alignment/ctc.py:32-121).
+
+    This is the true gradient of loglik with respect to log_probs taken as free variables,
+    +sum gamma (each frame's row sums to 1 for a feasible pair).  torch's ctc_loss backward does
+    NOT return that: it returns exp(log_probs) - sum gamma at log_probs, i.e. the gradient of the
+    loss with log_softmax's Jacobian already folded in (its rows sum to 0, not -1).  The two
+    conventions agree only once both are taken back through a log_softmax to the logits, where
+    d(-loglik)/d logits = softmax - sum gamma either way; compare them there.
+
+        loglik = CTCLogLik.apply(log_probs, targets, input_lengths, target_lengths, blank)
+    """
+
+    @staticmethod
+    def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank=0):
+        from . import ops
+        loglik, alpha, beta, _, _ = ops.ctc(log_probs.detach(), targets, input_lengths, target_lengths, int(blank),
+                                            alpha=True, beta=True)
+        ctx.save_for_backward(alpha, beta, loglik, targets, torch.as_tensor(input_lengths),
+                              torch.as_tensor(target_lengths))
+        ctx.blank, ctx.classes, ctx.dtype = int(blank), log_probs.shape[2], log_probs.dtype
+        return loglik
+
+    @staticmethod
+    def backward(ctx, grad_loglik):
+        from . import ops
+        alpha, beta, loglik, targets, il, tl = ctx.saved_tensors
+        grad, _ = ops.ctc_grad(alpha, beta, loglik, targets, il, tl, ctx.classes, ctx.blank)
+        grad = grad * grad_loglik.to(grad.dtype)[None, :, None]
+        return grad.to(ctx.dtype), None, None, None, None

@@ -17,6 +17,10 @@ shape-only fake implementations; their only real implementation is the HIP libra
       -> (cost_matrix, total, path_i, path_j, path_len)
   torch.ops.hmm355.soft_dtw(dist, gamma, n_len, m_len) -> (R, total)
   torch.ops.hmm355.soft_dtw_grad(dist, R, gamma, n_len, m_len) -> E
+  torch.ops.hmm355.ctc(log_probs, targets, input_lengths, target_lengths, blank, alpha, beta, viterbi)
+      -> (loglik, alpha, beta, path, score)
+  torch.ops.hmm355.ctc_grad(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes,
+                            blank, want_gamma) -> (grad, gamma)
 """
 from typing import Optional, Tuple
 
@@ -694,3 +698,147 @@ def soft_dtw_grad(dist: Tensor, R: Tensor, gamma: float, n_len: Optional[Tensor]
 @soft_dtw_grad.register_fake
 def _(dist, R, gamma, n_len=None, m_len=None):
     return dist.new_empty(tuple(dist.shape), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------ CTC lattice
+CTC_ALPHA = nat.CTC_ALPHA
+CTC_BETA = nat.CTC_BETA
+CTC_VITERBI = nat.CTC_VITERBI
+CTC_MAX_TARGET = nat.CTC_MAX_TARGET
+
+
+def _ctc_args(shape, dev, targets, input_lengths, target_lengths, blank):
+    """Checks the arguments of a CTC call over log_probs of `shape` = (T,B,C) on the host
+    (ValueError) and returns (int32 targets (B, max(Lmax, 1)), int32 input and target lengths, all
+    on `dev`, blank, Lmax as the caller gave it): the layout the C ABI takes.  The lengths (B
+    values each) are read on the host; that and the label check are the call's two
+    synchronisations."""
+    T, B, C = shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError(f"log_probs needs at least one frame, sequence and class; got {tuple(shape)}")
+    if targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError(f"targets must be (B, Lmax) with B = {B}; got {tuple(targets.shape)}")
+    if targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise ValueError(f"targets must hold integer labels; got {targets.dtype}")
+    Lmax = targets.shape[1]
+    if Lmax > CTC_MAX_TARGET:
+        raise ValueError(f"targets longer than {CTC_MAX_TARGET} labels are not supported; got {Lmax}")
+    blank = int(blank)
+    if not 0 <= blank < C:
+        raise ValueError(f"blank must lie in [0, {C}); got {blank}")
+    lens = []
+    for name, t, lo, hi in (("input_lengths", input_lengths, 1, T), ("target_lengths", target_lengths, 0, Lmax)):
+        t = torch.as_tensor(t)
+        if t.numel() != B:
+            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
+        host = t.detach().reshape(B).to("cpu", torch.int64)
+        if int(host.min()) < lo or int(host.max()) > hi:
+            raise ValueError(f"{name} must lie in [{lo}, {hi}]; got {host.tolist()}")
+        lens.append(host.to(torch.int32).to(dev))
+    tg = targets.detach().to(device=dev, dtype=torch.int32)
+    if Lmax == 0:
+        tg = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+    else:
+        used = torch.arange(Lmax, device=dev)[None, :] < lens[1][:, None]
+        if bool((((tg < 0) | (tg >= C)) & used).any()):
+            raise ValueError(f"targets hold labels outside [0, {C})")
+    return tg.contiguous(), lens[0], lens[1], blank, Lmax
+
+
+@torch.library.custom_op("hmm355::ctc", mutates_args=())
+def ctc(log_probs: Tensor, targets: Tensor, input_lengths: Tensor, target_lengths: Tensor, blank: int = 0,
+        alpha: bool = False, beta: bool = False, viterbi: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The CTC lattice of B sequences in one launch (hmm355_ctc_f32, csrc/ctc.hip).  log_probs
+    (T,B,C), targets (B,Lmax) integer labels, input_lengths / target_lengths (B) on any device.
+    Returns (loglik (B); alpha (B,T,2 Lmax+1); beta (B,T,2 Lmax+1), the reference's convention
+    without the frame's own emission; path (B,T) int32 expanded positions of the best single
+    path, -1 past input_lengths[b] and for a pair with no alignment; score (B) of that path).
+    alpha / beta / viterbi select what is computed beyond loglik; the others come back as empty
+    tensors, and with none of them no (B,T,S') table is written.  Lengths outside
+    [1, T] / [0, Lmax], labels outside [0, C) and a blank outside [0, C) raise ValueError (the
+    reference would index row -1)."""
+    nat.require_gpu(log_probs, targets)
+    if log_probs.dim() != 3:
+        raise ValueError(f"log_probs must be (T, B, C); got {tuple(log_probs.shape)}")
+    dev = log_probs.device
+    tg, il, tl, blank, Lmax = _ctc_args(log_probs.shape, dev, targets, input_lengths, target_lengths, blank)
+    lp = _f32c(log_probs.detach())
+    T, B, C = lp.shape
+    Lk = tg.shape[1]
+    Sk = 2 * Lk + 1
+    A = torch.empty((B, T, Sk) if alpha else _EMPTY, device=dev)
+    Bt = torch.empty((B, T, Sk) if beta else _EMPTY, device=dev)
+    loglik = torch.empty(B, device=dev)
+    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    score = torch.empty(B if viterbi else 0, device=dev)
+    flags = (CTC_ALPHA if alpha else 0) | (CTC_BETA if beta else 0) | (CTC_VITERBI if viterbi else 0)
+    L = nat.lib()
+    ws = _workspace(L.hmm355_ctc_workspace_bytes(B, T, Lk, flags), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_ctc_f32(
+            nat.ptr(lp), nat.ptr(tg), nat.ptr(il), nat.ptr(tl), T, B, C, Lk, blank, flags,
+            nat.ptr(A) if alpha else None, nat.ptr(Bt) if beta else None, nat.ptr(loglik),
+            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
+            nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    if Lk != Lmax:  # an empty targets matrix: the lattice is the single blank position
+        if alpha:
+            A = A[:, :, :1].contiguous()
+        if beta:
+            Bt = Bt[:, :, :1].contiguous()
+    return loglik, A, Bt, path, score
+
+
+@ctc.register_fake
+def _(log_probs, targets, input_lengths, target_lengths, blank=0, alpha=False, beta=False, viterbi=False):
+    T, B, _ = log_probs.shape
+    S = 2 * targets.shape[1] + 1
+    f32 = torch.float32
+    return (log_probs.new_empty(B, dtype=f32),
+            log_probs.new_empty((B, T, S) if alpha else _EMPTY, dtype=f32),
+            log_probs.new_empty((B, T, S) if beta else _EMPTY, dtype=f32),
+            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
+            log_probs.new_empty(B if viterbi else 0, dtype=f32))
+
+
+
+
+@torch.library.custom_op("hmm355::ctc_grad", mutates_args=())
+def ctc_grad(alpha: Tensor, beta: Tensor, loglik: Tensor, targets: Tensor, input_lengths: Tensor,
+             target_lengths: Tensor, num_classes: int, blank: int = 0,
+             want_gamma: bool = False) -> Tuple[Tensor, Tensor]:
+    """(grad (T,B,C), gamma (B,T,S') or empty) from the alpha, beta and loglik of one ops.ctc call
+    (hmm355_ctc_grad_f32): gamma = exp(alpha + beta - loglik) and grad[t,b,c] =
+    d loglik[b] / d log_probs[t,b,c] = the sum of gamma over the positions of class c.  Zero in
+    frames past input_lengths[b] and for a pair with no alignment; the same bits on every call."""
+    nat.require_gpu(alpha, beta, loglik, targets)
+    if alpha.dim() != 3 or alpha.shape != beta.shape:
+        raise ValueError(f"alpha and beta must both be (B, T, S'); got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+    B, T, S = alpha.shape
+    C = int(num_classes)
+    if loglik.numel() != B:
+        raise ValueError(f"loglik must hold one value per sequence ({B}); got {tuple(loglik.shape)}")
+    if targets.dim() != 2 or S != 2 * targets.shape[1] + 1:
+        raise ValueError(f"alpha has {S} positions; targets {tuple(targets.shape)} do not expand to that many")
+    dev = alpha.device
+    tg, il, tl, blank, Lmax = _ctc_args((T, B, C), dev, targets, input_lengths, target_lengths, blank)
+    alpha, beta, loglik = _f32c(alpha), _f32c(beta), _f32c(loglik)
+    Lk = tg.shape[1]
+    if Lk != Lmax:  # an empty targets matrix: widen the single blank column to the kernel's Lmax = 1
+        pad = alpha.new_full((B, T, 2), float("-inf"))
+        alpha, beta = torch.cat([alpha, pad], 2).contiguous(), torch.cat([beta, pad], 2).contiguous()
+    grad = torch.empty((T, B, C), device=dev)
+    gamma = torch.empty((B, T, 2 * Lk + 1) if want_gamma else _EMPTY, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().hmm355_ctc_grad_f32(
+            nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(tg), nat.ptr(il), nat.ptr(tl), T, B, C, Lk, blank,
+            nat.ptr(gamma) if want_gamma else None, nat.ptr(grad), nat.stream_of(dev)))
+    if want_gamma and Lk != Lmax:
+        gamma = gamma[:, :, :1].contiguous()
+    return grad, gamma
+
+
+@ctc_grad.register_fake
+def _(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes, blank=0, want_gamma=False):
+    B, T, S = alpha.shape
+    return (alpha.new_empty((T, B, num_classes), dtype=torch.float32),
+            alpha.new_empty((B, T, S) if want_gamma else _EMPTY, dtype=torch.float32))
