@@ -60,6 +60,16 @@ extern "C" {
  * when the 3B workgroups would not fit the device at once.  Passing it with a plan that is not banded is a caller error: posterior and
  * lik_ref come back NaN. */
 #define HMM355_FB_PLAN_BANDED 0x200u
+/* With HMM355_FB_PLAN_BANDED and T >= 256 each chain's own workgroup forms the posterior of the
+ * rows of its last two 16-step blocks (the first 17..32 times for the backward chain, the last
+ * for the forward chain) from the rows still in its LDS when it ends, instead of handing them to
+ * the followers through memory (csrc/recur.h rec_band, end rows).  Results are bit-identical
+ * with and without.  Two switches for tests and A/B timing:
+ * NO_END_ROWS turns that off (the followers form every row); END_ROWS_ODD_LEFT makes the chains
+ * leave the end rows of every odd 16-step block to the followers, the path taken when a partner
+ * chain's rows are not yet published. */
+#define HMM355_FB_NO_END_ROWS 0x400u
+#define HMM355_FB_END_ROWS_ODD_LEFT 0x800u
 
 const char* hmm355_strerror(int code);
 int hmm355_version(void);
@@ -162,8 +172,11 @@ int hmm355_viterbi_plan_f32(const float* obs, int obs_mode, const float* log_P, 
  * one extra workgroup per sequence forms log(x + 1e-8) of the emissions ahead of the chain
  * (OBS_PROB), composes the 64-step chunk maps from the psi rows the chain publishes, and
  * backtraces the path once the chain is done -- one launch instead of four.  Ignored when the 2B
- * workgroups would not fit the device at once or T exceeds what the follower's LDS holds
- * (~32k steps at N <= 128, ~16k at N <= 256).  Passing the flag with a plan that is not banded
+ * workgroups would not fit the device at once or T exceeds what the follower's LDS holds:
+ * csrc/follow.h vit_follow_lds_bytes(T, NP) <= 160 KiB, that is ceil(T / 64) * (NP + 4) <= 98240
+ * with NP = 128 for N <= 128 and 256 above -- T <= 47616 and T <= 24128.  (The follower keeps its
+ * end-state table, which spares the walk over the chunk maps at the end, while that fits as well:
+ * vit_follow_lds_bytes(T, NP, true) <= 160 KiB, T <= 16128 and T <= 8000.)  Passing the flag with a plan that is not banded
  * is a caller error: the states come back as -1 and the final score as NaN. */
 #define HMM355_VIT_PLAN_BANDED 0x1u
 /* HMM355_VIT_PLAN_DENSE: the caller read hmm355_plan_banded(plan) == 0.  Then, for N <= 128, the

@@ -16,6 +16,8 @@ OBS_LOG = 1
 FB_POSTERIOR = 1
 FB_PAIR = 0x100
 FB_PLAN_BANDED = 0x200  # HMM355_FB_PLAN_BANDED
+FB_NO_END_ROWS = 0x400  # HMM355_FB_NO_END_ROWS
+FB_END_ROWS_ODD_LEFT = 0x800  # HMM355_FB_END_ROWS_ODD_LEFT
 VIT_PLAN_BANDED = 0x1  # HMM355_VIT_PLAN_BANDED
 VIT_PLAN_DENSE = 0x2  # HMM355_VIT_PLAN_DENSE
 PLAN_DENSE = 0x1  # HMM355_PLAN_DENSE

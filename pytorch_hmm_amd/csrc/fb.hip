@@ -215,6 +215,15 @@ HMM355_API int hmm355_forward_backward_plan_f32(const float* obs, int obs_mode, 
     fa.pub = fb.pub = w.pub;
     fa.lik_ref = lik_ref;
     nfollow = HMM355_FBF > 0 ? HMM355_FBF : (4 * B <= fb_device_cus() ? 2 : 1);
+    // end rows (post.h kEndBlocks): each chain's own workgroup forms the posterior of its last
+    // 16 * kEndBlocks rows, so nothing is left to form once the chains end.  Shorter sequences
+    // keep the followers' form: the two ends would need each other's fresh rows.
+    if (T >= kEndMinT && !(out_mask & HMM355_FB_NO_END_ROWS)) {
+      fa.ends = fb.ends = kEndsOn | ((out_mask & HMM355_FB_END_ROWS_ODD_LEFT) ? kEndsOddLeft : 0u);
+      fa.prow = w.V;
+      fb.prow = w.U;
+      fa.post = fb.post = posterior;
+    }
   }
   PostArgs pa{w.U, w.V, w.LA, w.LB, posterior, forward, backward, lik_ref, B, T, N,
               out_mask & (HMM355_FB_POSTERIOR)};

@@ -14,13 +14,18 @@
 //   vit_decode_follow  (Viterbi) composes the 64-step chunk maps G_c[j] = state at the chunk's
 //                      first step - 1 given state j at its last (post.h compose_chunk_map's
 //                      map) from the psi rows the chain's helpers publish, storing each chunk's
-//                      path for every end state on the way; once the chain is complete, the
-//                      backtrace (hmm.py:174-178) is the first argmax of the last trellis row,
-//                      the walk over the maps, and a gather of every chunk's path at its end
-//                      state, all in this workgroup.
+//                      path for every end state on the way, and keeping the table of chunk end
+//                      states for every state at the end of the last composed chunk; once the
+//                      chain is complete, the backtrace (hmm.py:174-178) is the first argmax of
+//                      the last trellis row (taken by the chain's workgroup from its LDS and
+//                      polled with the count), one row of that table, and a gather of every
+//                      chunk's path at its end state, all in this workgroup.
 //   fb_post_follow     (forward-backward) the posterior (hmm.py:119-126) of every row t as soon
 //                      as both chains have published it: rows from the middle outwards, two per
-//                      chain step in the second half.
+//                      chain step in the second half.  With end rows (post.h kEndBlocks) the
+//                      rows of each chain's last two blocks are formed by that chain's own
+//                      workgroup from its LDS, and the follower takes only those a left-over
+//                      word names.
 //
 // Hand-off (common.h; MI355X_MICROARCH.md inter-workgroup visibility, the table's first row):
 // the chains' helpers store rows and psi bytes write-through (sc1), retire them before a
@@ -64,6 +69,42 @@ __device__ __forceinline__ void follow_poll(const int* p, int need, int* slot, u
     }
   }
   *slot = have;
+}
+
+// follow_poll for the Viterbi chain's count with its end word (post.h kVitEndWord), which the
+// chain stores well ahead of the final count: every poll loads both, so the end word costs no
+// round trip of its own behind the final count.  The end word names its call (vit_end_tag), so
+// one loaded beside the count -- not after it -- is known to be this call's; a final count
+// whose end word does not (yet) carry the tag reads as nblocks, and the next poll has it.
+// slot[0]: the count (-1 on give-up), slot[1], slot[2]: the end state and the score's bits.
+__device__ __forceinline__ void follow_poll_end(const int* p, int need, int* slot, unsigned token, int nblocks) {
+  const unsigned tag = vit_end_tag(token);
+  unsigned long long e = 0;
+  auto poll = [&]() -> int {
+    const unsigned long long* pe = reinterpret_cast<const unsigned long long*>(p + kVitEndWord);
+    const unsigned long long ev = __hip_atomic_load(pe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int c = poll_count(p, token, nblocks + 1);
+    if (c <= nblocks) return c;
+    e = ev;
+    return ((unsigned)ev >> 8) == tag ? c : nblocks;
+  };
+  int have = poll(), last = have;
+  long long t0 = __builtin_amdgcn_s_memrealtime();
+  while (have < need) {
+    __builtin_amdgcn_s_sleep(20);
+    have = poll();
+    const long long now = __builtin_amdgcn_s_memrealtime();
+    if (have != last) {
+      last = have;
+      t0 = now;
+    } else if (now - t0 > kFollowGiveUp) {
+      have = -1;
+      break;
+    }
+  }
+  slot[0] = have;
+  slot[1] = (int)((unsigned)e & 0xffu);
+  slot[2] = (int)(unsigned)(e >> 32);
 }
 
 // ------------------------------------------------------------------------ log leaders
@@ -115,13 +156,15 @@ __device__ __forceinline__ void vit_lead(const RecArgs& a, int b) {
 
 // ------------------------------------------------------------- Viterbi decode follower
 // LDS: chunk maps [nc][NP] | staging of up to G chunks' psi rows [G][64][NP] | chunk end
-// states [nc] | control words.  The host admits the follower path only while it fits
-// (vit_follow_lds_bytes <= kExclusiveLds).
+// states [nc] | control words | (table) the end-state table, two copies [2][NP][nc up to 4].
+// The host admits the follower path only while it fits without the table
+// (vit_follow_lds_bytes <= kExclusiveLds), and the table (RecArgs::vit_table) while that fits too.
 // chunks composed at once: NP lanes each, 1024 threads, at most 8 (64 KiB of staged rows)
 __host__ __device__ constexpr int follow_g(int NP) { return 1024 / NP < 8 ? 1024 / NP : 8; }
-inline size_t vit_follow_lds_bytes(int T, int NP) {
+inline size_t vit_follow_lds_bytes(int T, int NP, bool table = false) {
   const size_t nc = (T + kChunk - 1) / kChunk;
-  return align_up(nc * NP, 16) + (size_t)follow_g(NP) * kChunk * NP + align_up(nc, 4) * 4 + 64;
+  return align_up(nc * NP, 16) + (size_t)follow_g(NP) * kChunk * NP + align_up(nc, 4) * 4 + 64 +
+         (table ? 2 * (size_t)NP * align_up(nc, 4) : 0);
 }
 
 template <int NP>
@@ -133,6 +176,14 @@ __device__ __forceinline__ void vit_decode_follow(const RecArgs& a, int b, float
   uint8_t* stg = gm + align_up((size_t)nc * NP, 16);             // [G][64][NP]
   int* send = reinterpret_cast<int*>(stg + (size_t)follow_g(NP) * kChunk * NP);  // [nc]
   int* ctl = send + align_up((size_t)nc, 4);                     // control words
+  // The end-state table: S[j][c'] = the state at the end of chunk c' given state j at the end of
+  // the last composed chunk c (c' < c).  Adding chunk c + 1 is S'[j] = S[G_{c+1}[j]] followed by
+  // G_{c+1}[j] -- done between the publishes, while the chain runs; once the chain's end state
+  // is known the chunk end states are one row of it, and no map is walked at the end.
+  const bool tab = a.vit_table != 0;
+  const int ncp = (int)align_up((size_t)nc, 4), nq = ncp / 4;
+  unsigned* const stab = reinterpret_cast<unsigned*>(ctl + 16);  // [2][NP][nq] dwords
+  int scur = 0;
   int64_t* sb = a.states + (size_t)b * T;
   auto invalid = [&]() {  // the chain never published (a dense plan passed as banded, or stalled)
     for (int t = tid; t < T; t += blockDim.x) sb[t] = -1;
@@ -149,10 +200,16 @@ __device__ __forceinline__ void vit_decode_follow(const RecArgs& a, int b, float
   constexpr int G = follow_g(NP);
   int have = 0;   // psi blocks published (nblocks + 1: everything)
   int next = 0;   // the next chunk to compose (chunk 0 for its paths; its map is unused)
+  int end_state = 0;       // the chain's end word, read with the final count
+  float end_score = 0.f;
   auto wait_for = [&](int need) -> bool {
-    if (tid == 0) follow_poll(pubp, need, ctl, a.token, nblocks + 1);
+    if (tid == 0) follow_poll_end(pubp, need, ctl, a.token, nblocks);
     __syncthreads();
     const int v = ctl[0];
+    if (v > nblocks) {
+      end_state = ctl[1];
+      end_score = __builtin_bit_cast(float, ctl[2]);
+    }
     __syncthreads();
     if (v < 0) return false;
     have = v;
@@ -204,6 +261,24 @@ __device__ __forceinline__ void vit_decode_follow(const RecArgs& a, int b, float
       next += cnt;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the paths stored before the barrier)
       __syncthreads();
+      if (tab) {
+        // the table through the group's chunks, one after the other (bytes [0, c) of a row are
+        // defined after chunk c; what lies beyond is never read)
+        for (int c = next - cnt < 1 ? 1 : next - cnt; c < next; ++c) {
+          const unsigned* src = stab + (size_t)scur * NP * nq;
+          unsigned* dst = stab + (size_t)(scur ^ 1) * NP * nq;
+          const int nd = (c - 1) / 4 + 1, sh = 8 * ((c - 1) & 3);
+          for (int idx = tid; idx < NP * nd; idx += blockDim.x) {
+            const int j = idx / nd, d = idx - j * nd;
+            const unsigned g = gm[(size_t)c * NP + j];
+            unsigned wv = src[g * nq + d];
+            if (d == nd - 1) wv = (wv & ~(0xffu << sh)) | (g << sh);
+            dst[j * nq + d] = wv;
+          }
+          scur ^= 1;
+          __syncthreads();
+        }
+      }
     }
   };
   // while the chain runs: every chunk whose four psi blocks are published
@@ -224,20 +299,16 @@ __device__ __forceinline__ void vit_decode_follow(const RecArgs& a, int b, float
     return;
   }
   fstamp(1);
-  // s_{T-1} = first argmax of delta_{T-1} (hmm.py:174); the maps from the last chunk down
-  if (w == 0) {
-    const float* dl = a.rows + ((size_t)b * T + T - 1) * a.row_stride;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < NP / 64; ++k) {
-      const int j = l + 64 * k;
-      const float v = __hip_atomic_load(dl + (j < N ? j : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (j < N) argmax_combine(bv, bi, v, j);
-    }
-    wave_argmax_dpp(bv, bi);
-    if (l == 0 && a.final_score) a.final_score[b] = bv;
-    int s = bi < N ? bi : 0;
+  // s_{T-1} = first argmax of delta_{T-1} (hmm.py:174), taken by the chain's workgroup from its
+  // LDS row (recur.h rec_band) and read with the final count.  The chunk end states are row
+  // s_{T-1} of the table; without the table, the walk over the maps.
+  const int send_last = (unsigned)end_state < (unsigned)N ? end_state : 0;
+  if (tid == 0 && a.final_score) a.final_score[b] = end_score;
+  if (tab) {
+    const uint8_t* srow = reinterpret_cast<const uint8_t*>(stab + ((size_t)scur * NP + send_last) * nq);
+    for (int c = tid; c < nc; c += blockDim.x) send[c] = c == nc - 1 ? send_last : srow[c];
+  } else if (w == 0) {
+    int s = send_last;
     if (l == 0) send[nc - 1] = s;
     for (int c = nc - 1; c >= 1; --c) {
       s = gm[(size_t)c * NP + s];
@@ -308,61 +379,32 @@ __device__ __forceinline__ void fb_post_follow(const RecArgs& fa, const RecArgs&
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int tr = r < nv ? t[r] : t[0];
-      if constexpr (K == 1) {
-        u[r][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rU, (tr * NP + l) * 4, 0, kAuxSc1));
-        v[r][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rV, (tr * NP + l) * 4, 0, kAuxSc1));
-      } else if constexpr (K == 2) {
-        const float2 x = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rU, (tr * NP + 2 * l) * 4, 0, kAuxSc1));
-        const float2 y = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rV, (tr * NP + 2 * l) * 4, 0, kAuxSc1));
-        u[r][0] = x.x; u[r][1] = x.y; v[r][0] = y.x; v[r][1] = y.y;
-      } else {
-        const float4 x = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rU, (tr * NP + 4 * l) * 4, 0, kAuxSc1));
-        const float4 y = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rV, (tr * NP + 4 * l) * 4, 0, kAuxSc1));
-        u[r][0] = x.x; u[r][1] = x.y; u[r][2] = x.z; u[r][3] = x.w;
-        v[r][0] = y.x; v[r][1] = y.y; v[r][2] = y.z; v[r][3] = y.w;
-      }
+      post_row_load<K>(rU, tr, l, u[r]);
+      post_row_load<K>(rV, tr, l, v[r]);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (r >= nv) break;
-      const int t_ = t[r];
-      // post.h fb_posterior_kernel: max-normalised product, normalised by its sum
-      float mu = 0.f, mv = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) { mu = fmaxf(mu, u[r][k]); mv = fmaxf(mv, v[r][k]); }
-      mu = wave_max_dpp2(mu);
-      mv = wave_max_dpp2(mv);
-      const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
-      float p[K], sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) { p[k] = (u[r][k] * iu) * (v[r][k] * iv); sum += p[k]; }
-      sum = wave_sum_dpp(sum);
-      const float is = sum > 0.f ? 1.f / sum : 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) p[k] *= is;
-      if (vec) {
-        float* dst = pbase + (size_t)t_ * N + K * l;
-        if constexpr (K == 1) dst[0] = p[0];
-        else if constexpr (K == 2) *reinterpret_cast<float2*>(dst) = make_float2(p[0], p[1]);
-        else *reinterpret_cast<float4*>(dst) = make_float4(p[0], p[1], p[2], p[3]);
-      } else {
-        // (not vec: lane l holds states K*l .. K*l + K - 1 all the same)
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-          if (K * l + k < N) pbase[(size_t)t_ * N + K * l + k] = p[k];
-      }
+      post_row_lanes<K>(u[r], v[r], pbase + (size_t)t[r] * N, N, l, vec);
     }
   };
+  // with end rows (post.h kEndBlocks; the host: fb.hip) the chains' own workgroups form the rows
+  // of their last kEndBlocks blocks -- chain rows [qend0, T): times [qend0, T) for alpha, times
+  // [0, T - qend0) for beta -- and the followers the interior [rlo, rhi) plus what the left-over
+  // words name
+  const bool ends = (fa.ends & kEndsOn) != 0;
+  const int qend0 = 16 * (nblocks - kEndBlocks), nend = T - qend0;
+  const int rlo = ends ? nend : 0, rhi = ends ? qend0 : T;
   int plo = -1, phi = -1;  // done rows [plo, phi); empty while plo < 0
   int ca = 0, cb = 0;
-  while (plo != 0 || phi != T) {
+  while (plo != rlo || phi != rhi) {
     // wait for rows beyond the done interval (one lane polls both chains)
     if (tid == 0) {
       int ok = 1;
       long long t0 = __builtin_amdgcn_s_memrealtime();
       for (;;) {
         const int na = poll_count(pa, fa.token, nblocks + 1), nb = poll_count(pb_, fa.token, nblocks + 1);
-        const int lo = T - rows_of(nb), hi = rows_of(na);
+        const int lo = max(T - rows_of(nb), rlo), hi = min(rows_of(na), rhi);
         const bool more = lo < hi && (plo < 0 || lo < plo || hi > phi);
         if (more) { ca = na; cb = nb; break; }
         if (na != ca || nb != cb) { ca = na; cb = nb; t0 = __builtin_amdgcn_s_memrealtime(); }
@@ -381,7 +423,7 @@ __device__ __forceinline__ void fb_post_follow(const RecArgs& fa, const RecArgs&
       return;
     }
     if (kStamp && ca > nblocks && cb > nblocks) fstamp(1);
-    const int lo = T - rows_of(cb), hi = rows_of(ca);
+    const int lo = max(T - rows_of(cb), rlo), hi = min(rows_of(ca), rhi);
     // new rows: [lo, plo) and [phi, hi) (all of [lo, hi) the first time); this follower's are
     // those with t % F == f
     const int a0 = first_own(lo), a1 = plo < 0 ? hi : plo;
@@ -397,6 +439,44 @@ __device__ __forceinline__ void fb_post_follow(const RecArgs& fa, const RecArgs&
     }
     plo = lo;
     phi = hi;
+  }
+  if (ends) {
+    // The left-over words: each chain's helpers publish theirs as the chain ends.  Normally both
+    // are empty and the follower is done; a named block's end rows need that chain's last
+    // flushes and the partner's rows, so they wait for both final counts.
+    if (tid == 0) {
+      follow_poll(pa + kLeftWord, (int)kLeftValid, ctl + 1, fa.token, (int)kLeftCap);
+      follow_poll(pb_ + kLeftWord, (int)kLeftValid, ctl + 2, fa.token, (int)kLeftCap);
+      int ok = ctl[1] >= 0 && ctl[2] >= 0;
+      if (ok && ((ctl[1] | ctl[2]) & (int)(kLeftValid - 1u))) {
+        follow_poll(pa, nblocks + 1, ctl, fa.token, nblocks + 1);
+        ok = ctl[0] >= 0;
+        if (ok) {
+          follow_poll(pb_, nblocks + 1, ctl, fa.token, nblocks + 1);
+          ok = ctl[0] >= 0;
+        }
+      }
+      ctl[0] = ok;
+    }
+    __syncthreads();
+    const int ok = ctl[0], left[2] = {ctl[1], ctl[2]};
+    __syncthreads();
+    if (!ok) {
+      invalid();
+      return;
+    }
+    if (kStamp) fstamp(1);
+    if ((left[0] | left[1]) & (int)(kLeftValid - 1u)) {
+      // chain row q of direction d is time q (alpha) / T - 1 - q (beta); one row per wave per pass
+      for (int i = w; i < 2 * nend; i += nw) {
+        const int d = i / nend, q = qend0 + i % nend;
+        const int tq = d ? T - 1 - q : q;
+        if (((left[d] >> (nblocks - 1 - (q >> 4))) & 1) && tq % F == f) {
+          const int t[R] = {tq};
+          rows(t, 1);
+        }
+      }
+    }
   }
   if (kStamp) {
     __syncthreads();

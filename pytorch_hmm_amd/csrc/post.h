@@ -21,6 +21,80 @@ struct PostArgs {
   unsigned mask;
 };
 
+// One posterior row formed by one wave from its scaled alpha row u and beta row v, lane l holding
+// states K*l .. K*l + K - 1: fb_posterior_kernel's rule (the max-normalised product, normalised
+// by its sum), stored to dst (the row's N floats; vec: N == NP and the row K-float aligned).
+// The posterior followers (follow.h) and the chain workgroups' end rows (recur.h rec_band) both
+// form their rows here, so a row has the same bits whoever forms it.
+template <int K>
+__device__ __forceinline__ void post_row_lanes(const float (&u)[K], const float (&v)[K], float* dst, int N, int l, bool vec,
+                                               bool on = true) {
+  float mu = 0.f, mv = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) { mu = fmaxf(mu, u[k]); mv = fmaxf(mv, v[k]); }
+  mu = wave_max_dpp2(mu);
+  mv = wave_max_dpp2(mv);
+  const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+  float p[K], sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) { p[k] = (u[k] * iu) * (v[k] * iv); sum += p[k]; }
+  sum = wave_sum_dpp(sum);
+  const float is = sum > 0.f ? 1.f / sum : 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) p[k] *= is;
+  if (!on) return;  // (wave-uniform: a row the caller computes but does not own)
+  if (vec) {
+    if constexpr (K == 1) dst[l] = p[0];
+    else if constexpr (K == 2) *reinterpret_cast<float2*>(dst + 2 * l) = make_float2(p[0], p[1]);
+    else *reinterpret_cast<float4*>(dst + 4 * l) = make_float4(p[0], p[1], p[2], p[3]);
+  } else {
+    // (not vec: lane l holds states K*l .. K*l + K - 1 all the same)
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (K * l + k < N) dst[K * l + k] = p[k];
+  }
+}
+// a row of U or V in that layout, by sc1 loads (rs: the sequence's rows, NP floats each)
+template <int K>
+__device__ __forceinline__ void post_row_load(const __amdgpu_buffer_rsrc_t rs, int t, int l, float (&x)[K]) {
+  const int off = (t * 64 * K + K * l) * 4;
+  if constexpr (K == 1) {
+    x[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, kAuxSc1));
+  } else if constexpr (K == 2) {
+    const float2 y = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, kAuxSc1));
+    x[0] = y.x; x[1] = y.y;
+  } else {
+    const float4 y = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, kAuxSc1));
+    x[0] = y.x; x[1] = y.y; x[2] = y.z; x[3] = y.w;
+  }
+}
+
+// The forward-backward end rows (recur.h rec_band, follow.h): the rows of the last kEndBlocks
+// 16-step blocks of each chain -- chain rows q >= 16 * (nblocks - kEndBlocks): the first for beta,
+// the last for alpha in time -- get their posterior in the chain's own workgroup once the chain
+// has ended, from its LDS ring and the partner chain's rows published long before.  Two blocks:
+// what the helpers flush after the chain's last step.  (Nine, the helpers' worst publish lag,
+// formed beside the running chain cost the chains more than the tail it saved: DESIGN section 14.)
+constexpr int kEndBlocks = 2;
+// shortest T with end rows: the partner's first rows are counted by its block 9 (its first
+// publish), so by the time a chain of 16 blocks polls before its last one
+constexpr int kEndMinT = 256;
+// the chain's last blocks in which the helpers publish every block instead of every fourth
+constexpr int kLateBlocks = 12;
+// RecArgs::ends
+constexpr unsigned kEndsOn = 1u, kEndsOddLeft = 2u;
+// the left-over word beside a chain's count (common.h publish_count's form): bit i = the chain's
+// block nblocks - 1 - i holds end rows the helpers left to the followers, kLeftValid always
+constexpr int kLeftWord = 2;  // ints past the count
+constexpr unsigned kLeftValid = 0x8000u, kLeftCap = 0xffffu;
+
+// Viterbi with a decode follower: the end word {end state | call tag << 8, the state's score} of
+// the last trellis row, stored by the chain's helpers this many ints past the published count
+// before the final publish.  The tag (24 bits of the count token's mix, never 0: a zeroed word
+// carries none) tells this call's word from whatever the workspace held before.
+constexpr int kVitEndWord = 2;
+__device__ __forceinline__ unsigned vit_end_tag(unsigned token) { return ((count_mix(token) >> 8) | 1u) & 0xffffffu; }
+
 constexpr int kPostWaves = 32768;  // waves of the posterior pass (grid-stride; 8192 measured 2.4 us slower than 16384)
 
 template <int NP>

@@ -29,6 +29,7 @@
 #include "band.h"
 #include "common.h"
 #include "logcr.h"
+#include "post.h"
 
 namespace hmm355 {
 
@@ -55,6 +56,9 @@ struct RC {
   static constexpr int OFF_LOGT = OFF_M + MRING;           // [256] doubles: Viterbi log table (logcr.h)
   static constexpr int LDS_FLOATS = OFF_LOGT + 512;
   static_assert(LDS_FLOATS * 4 <= kExclusiveLds, "LDS layout too large");
+  // forward-backward end rows (rec_band): each staging helper's left-over blocks, [16] words
+  static constexpr int OFF_LEFT = LDS_FLOATS;
+  static_assert((OFF_LEFT + 16) * 4 <= kExclusiveLds, "end-row LDS layout too large");
   // fused-psi Viterbi (kVitFused; the chain kernel owns all 160 KiB): the psi rows of the last
   // 64 steps (bytes [64][NP]), written by the psi waves, copied to HBM by the staging helpers
   static constexpr int PSR = 64;
@@ -384,7 +388,8 @@ struct RecArgs {
   // row copies (fused Viterbi) are write-through (sc1) stores, and one lane publishes how many
   // 16-step blocks of them are complete in pub[b * 2 + direction] (FB) / pub[b] (Viterbi):
   // blocks [0, pub) done while the chain runs, nblocks + 1 once everything (rows, psi, the last
-  // trellis row) is stored.  Null: no publishing.
+  // trellis row) is stored; the fused Viterbi chain leaves the path's end state and score in
+  // the word kVitEndWord ints past its count before that.  Null: no publishing.
   int* pub;
   // Viterbi with OBS_PROB emissions and log leaders (follow.h vit_lead): lobuf (B,T,N) holds
   // log(x + 1e-8) of 16-step blocks [4, lready[b]) of sequence b, written by the leaders; the
@@ -395,6 +400,12 @@ struct RecArgs {
   float* lik_ref;        // FB alpha with publishing: (B) the reference's compute_likelihood value
   uint8_t* path;         // Viterbi decode follower: (B, nchunks, NP, 64) chunk paths (follow.h)
   unsigned token;        // the published counts' call token (common.h poll_count / publish_count)
+  // FB end rows (post.h kEndBlocks; publishing chains only): the partner chain's rows (alpha: V,
+  // beta: U), the posterior output, and kEndsOn | kEndsOddLeft (0: the followers form every row)
+  const float* prow;
+  float* post;
+  unsigned ends;
+  int vit_table;         // Viterbi decode follower: keep the end-state table (follow.h; it fits the LDS)
 };
 constexpr int kProgSlots = 8;  // >= kRbHelpers<NP>::NH
 
@@ -1703,6 +1714,75 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
     // helper), and takes this block's poll.
     // (diagnostic builds: a helper's cycles of block work and at the barrier)
     unsigned long long hs_work = 0, hs_wait = 0;
+    // Forward-backward end rows (post.h kEndBlocks): the rows of the chain's last two blocks are
+    // still in the LDS ring when the chain ends, and were they left to the followers they would
+    // be flushed, published, seen by a polling lane and read back before their posterior could
+    // be formed.  The helpers form it here instead, helper hi rows hi, hi + NH .. of the two
+    // blocks, in the followers' lane layout with the followers' function (post_row_lanes): the
+    // own row from the ring (the values rec_flush stores), the partner chain's row -- written
+    // near that chain's start -- by sc1 loads issued while the chain runs its last block
+    // (end_load: the helpers only wait for the last barrier then), behind ONE poll of the
+    // partner's count.  Rows whose partner rows were not counted (a partner dispatched late) or
+    // that kEndsOddLeft names are left to the followers: the helper's bits go to its left-over
+    // word in LDS and helper 0 publishes the union right after the last barrier (follow.h reads
+    // it).  The chain workgroup polls once and never spins.
+    constexpr int KL = NP / 64;                               // states per lane in the followers' layout
+    constexpr int RE = (16 * kEndBlocks + NH - 1) / NH;       // end rows per helper
+    [[maybe_unused]] float epr[RE][KL];
+    [[maybe_unused]] int eok = 0;
+    const bool endson = FB && stager && pubon && (a.ends & kEndsOn) && a.prow && a.post;
+    const int qend0 = 16 * (nblocks - kEndBlocks);            // the first end row (chain order)
+    // end row m of this helper: chain row q, live when it exists
+    auto end_row = [&](int m, int& q) -> bool {
+      q = qend0 + hi + NH * m;
+      return q < T;
+    };
+    [[maybe_unused]] auto end_load = [&]() {
+      if constexpr (FB) {
+        const int* ppub = a.pub + (2 * b + (KIND == kFbAlpha)) * kPubStride;
+        const int cnt = __builtin_amdgcn_readfirstlane(poll_count(ppub, a.token, nblocks + 1));
+        // (the partner's rows of times tau(q), q >= qend0, are its own rows < T - qend0)
+        const bool counted = cnt > nblocks || 16 * cnt >= T - qend0;
+        int leftmask = 0;
+#pragma unroll
+        for (int m = 0; m < RE; ++m) {
+          int q;
+          const bool live = end_row(m, q);
+          const bool ok = counted && !((a.ends & kEndsOddLeft) && ((q >> 4) & 1));
+          eok |= (int)ok << m;
+          if (live && !ok) leftmask |= 1 << (nblocks - 1 - (q >> 4));
+          int tq = live ? rec_tau<KIND>(q, T) : 0;
+          asm volatile("" : "+v"(tq) : "s"(cnt));  // (the loads stay behind the count's poll)
+          post_row_load<KL>(make_rsrc(a.prow + (size_t)b * T * NP, (size_t)T * NP * 4), tq, l, epr[m]);
+        }
+        if (l == 0) reinterpret_cast<int*>(lds + C::OFF_LEFT)[hi] = leftmask;
+      }
+    };
+    [[maybe_unused]] auto end_post = [&]() {
+      if constexpr (FB) {
+        const bool endvec = N == NP && (reinterpret_cast<uintptr_t>(a.post) % (4 * KL)) == 0;
+#pragma unroll
+        for (int m = 0; m < RE; ++m) {
+          int q;
+          const bool on = end_row(m, q) && ((eok >> m) & 1);
+          const int tq = on ? rec_tau<KIND>(q, T) : 0;
+          float own[KL];
+          const float* rp = lds + C::OFF_RING + (q & (C::RING - 1)) * NP + KL * l;  // (unconditional read)
+          if constexpr (KL == 1) {
+            own[0] = rp[0];
+          } else if constexpr (KL == 2) {
+            const float2 y = *reinterpret_cast<const float2*>(rp);
+            own[0] = y.x; own[1] = y.y;
+          } else {
+            const float4 y = *reinterpret_cast<const float4*>(rp);
+            own[0] = y.x; own[1] = y.y; own[2] = y.z; own[3] = y.w;
+          }
+          float* dst = a.post + ((size_t)b * T + tq) * N;
+          if (KIND == kFbAlpha) post_row_lanes<KL>(own, epr[m], dst, N, l, endvec, on);
+          else post_row_lanes<KL>(epr[m], own, dst, N, l, endvec, on);
+        }
+      }
+    };
     auto block_work = [&](int kb, float(&ernext)[HV][5], float(&erfree)[HV][5], int& lp, auto FULLC) {
       asm volatile("" ::: "memory");  // (block_work(kb - 1)'s stores stay ahead of this block's loads)
       unsigned long long hs0 = 0;
@@ -1730,10 +1810,13 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
       psi_copy(kb - 3);
       if (KIND == kVit && a.lready) lp = poll_count(a.lready + b * kPubStride, a.token, nblocks);
       // every fourth block (Viterbi: whole 64-step chunks of psi rows), after this block's loads
-      // (so the stores it signals are never waited for sooner than three blocks on)
+      // (so the stores it signals are never waited for sooner than three blocks on); with end
+      // rows every block of the chain's last kLateBlocks, so that what the followers still have
+      // to form when the chain ends is one pass of theirs, not two
       if (pubon && !(kFAbl & fabl::kNoBlockPublish) && hi == 0 && l == 0) {
         const int cnt = FB ? kb - 5 : kb - 6;
-        if (cnt > 0 && (cnt & 3) == 0) publish_count(pubp, cnt, a.token);
+        const bool late = FB && (a.ends & kEndsOn) && kb >= nblocks - kLateBlocks;
+        if (cnt > 0 && ((cnt & 3) == 0 || late)) publish_count(pubp, cnt, a.token);
       }
       unsigned long long hs1 = 0;
       if (kStamp) { hs1 = stamp(); hs_work += hs1 - hs0; }
@@ -1770,7 +1853,38 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
       unsigned long long* o8 = g_rec_stamps + (((size_t)blockIdx.x * 16 + w) % kStampWaves) * 8;
       o8[0] = hs_work; o8[1] = hs_wait; o8[4] = (unsigned long long)nblocks;
     }
+    if (endson) end_load();  // (the chain runs its last block: the helpers only wait for it)
     lds_barrier();  // the chain's last row and c_{T-1}
+    if (endson && hi == 0 && l == 0) {
+      // every helper's left-over blocks were decided before the barrier: their union
+      int m = 0;
+      for (int h = 0; h < NH; ++h) m |= reinterpret_cast<const int*>(lds + C::OFF_LEFT)[h];
+      publish_count(const_cast<int*>(pubp) + kLeftWord, m | (int)kLeftValid, a.token);
+    }
+    if constexpr (FUSE) {
+      // The decode's end state (follow.h vit_decode_follow): the first arg-max of the last trellis
+      // row, taken here from the LDS ring with the reduction and the state-to-lane mapping the
+      // follower used (ties resolve as they did there), stored as the end word beside the count
+      // (post.h kVitEndWord) well ahead of the final publish: the follower polls it with the
+      // count and neither loads the row nor reduces it.
+      if (pubon && hi == 0) {
+        const float* dl = lds + C::OFF_RING + ((T - 1) & (C::RING - 1)) * NP;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int k = 0; k < NP / 64; ++k) {
+          const int j = l + 64 * k;
+          const float v = dl[j];
+          if (j < N) argmax_combine(bv, bi, v, j);
+        }
+        wave_argmax_dpp(bv, bi);
+        if (l == 0)
+          __hip_atomic_store(reinterpret_cast<unsigned long long*>(pubp + kVitEndWord),
+                             ((unsigned long long)__builtin_bit_cast(unsigned, bv) << 32) | (vit_end_tag(a.token) << 8) |
+                                 (unsigned)(bi < N ? bi : 0),
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
     if (FB && pubon && nblocks > 6) {
       // the loop's flushes (blocks < nblocks - 2) retired: published now, so the followers form
       // those rows while the last two blocks are flushed (the final count comes after them)
@@ -1791,6 +1905,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
           rec_flush<NP, KIND, 1>(a, lds, b, nblocks - 1, l + 64 * vw, lsv1);
         }
       }
+      if (endson) end_post();  // (the end rows' posterior while those stores retire)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();  // (the chain wave has ended: the helpers alone)
       if (hi == 0 && l == 0) publish_count(pubp, nblocks + 1, a.token);
@@ -1845,6 +1960,12 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
       __syncthreads();  // (the chain and psi waves have ended: the helpers alone)
       if (hi == 0 && l == 0) publish_count(pubp, nblocks + 1, a.token);
       if (kStamp && hi == 0 && l == 0) g_rec_stamps[((size_t)blockIdx.x * 16 % kStampWaves) * 8 + 2] = __builtin_amdgcn_s_memrealtime();
+    }
+    if (kStamp && hi == 0) {
+      // (diagnostic builds: when helper 0's last stores have retired -- the chain workgroup's exit,
+      // in entry 2 of its wave's record; tools/band_stamps.py)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (l == 0) g_rec_stamps[(((size_t)blockIdx.x * 16 + w) % kStampWaves) * 8 + 2] = __builtin_amdgcn_s_memrealtime();
     }
 }
 

@@ -346,6 +346,7 @@ hipError_t launch_vit(const VitArgs& va, bool prep, hipStream_t sm) {
     ra.lready = va.lready;
     ra.path = va.path;
     ra.token = va.token;
+    ra.vit_table = vit_follow_lds_bytes(va.T, NP, true) <= kExclusiveLds;
     hipLaunchKernelGGL(vit_fwd_kernel<NP>, dim3(2 * va.B), dim3(kVitNT<NP>), kExclusiveLds, sm, ra);
     return hipGetLastError();
   }

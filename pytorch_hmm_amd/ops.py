@@ -34,6 +34,9 @@ OBS_LOG = nat.OBS_LOG
 FB_POSTERIOR = nat.FB_POSTERIOR
 FB_PAIR = nat.FB_PAIR
 FB_PLAN_BANDED = nat.FB_PLAN_BANDED
+# test / A-B switches of the followers' end rows, passed in forward_backward's out_mask
+FB_NO_END_ROWS = nat.FB_NO_END_ROWS
+FB_END_ROWS_ODD_LEFT = nat.FB_END_ROWS_ODD_LEFT
 VIT_PLAN_BANDED = nat.VIT_PLAN_BANDED
 VIT_PLAN_DENSE = nat.VIT_PLAN_DENSE
 FORM_GENERAL = nat.FORM_GENERAL

@@ -49,6 +49,21 @@ def timeline(name, chains, fol, nstamp):
     print(msg, flush=True)
 
 
+def chain_exit(name, tag, nblk, t0):
+    """real-time (us) of the chain workgroups' exit (helper 0, wave 1, its stores retired): median
+    and last; a build without that stamp leaves the entry 0"""
+    sym = getattr(L, f"hmm355_debug_stamps_{tag}")
+    sym.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    n = 512 * 16 * 8
+    buf = (ctypes.c_ulonglong * n)()
+    assert sym(buf, n) == 0
+    x = np.frombuffer(buf, dtype=np.uint64).reshape(-1, NW, 8)[:nblk, 1, 2].astype(np.float64)
+    if x.min() <= 0:
+        print(f"  {name:10s} chain workgroups' exit: not stamped by this build")
+    else:
+        print(f"  {name:10s} chain workgroups' exit {float(np.median(x - t0)) / 100:6.1f} (last {(x - t0).max() / 100:6.1f})", flush=True)
+
+
 def helpers(name, tag, nblk, waves):
     """cycles per block of the staging helpers' work and their wait at the block barrier"""
     sym = getattr(L, f"hmm355_debug_stamps_{tag}")
@@ -105,8 +120,10 @@ for mode in ("fb", "vit", "both"):
         timeline("fb", late, r[2 * B:3 * B] if fl else None, 3)
         if fl:
             timeline("fb f1", late, r[3 * B:], 3)
+        chain_exit("fb", "fb", 2 * B, late[:, 0].min())
     if mode in ("vit", "both"):
         show("viterbi", read("vit", B))
         helpers("vit", "vit", B, (1, 2, 3, 9, 10, 11))
         r = raw("vit", 2 * B)
         timeline("vit", r[:B], r[B:] if fl else None, 4)
+        chain_exit("vit", "vit", B, r[:B, 0].min())
