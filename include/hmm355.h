@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024]                  */
@@ -537,6 +537,46 @@ int hmm355_ctc_grad_f32(const float* alpha, const float* beta, const float* logl
                         const int* targets, const int* input_lengths, const int* target_lengths,
                         int T, int B, int C, int Lmax, int blank, float* gamma, float* grad,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Duration-constrained Viterbi (csrc/dchmm.hip).  Replaces the t / s / prev_s loops of
+ * DurationConstrainedHMM._constrained_viterbi (hsmm.py:520-590): a Viterbi recursion with a
+ * run-length counter per cell and soft penalties that depend on the counters.  One launch per
+ * call, one workgroup per penalty group; no workgroup waits on another.
+ *   emis   (B,T,S) fp32 emission log-probs, log_T (S,S) fp32 log-transitions; -inf entries are
+ *          allowed, +inf and NaN are not.  log_T's diagonal is never read.
+ *   group  G in [1, B]: sequences [k G, min(B, (k+1) G)) share their penalties.  G = B is the
+ *          reference (it takes .max() / .min() over the whole batch, so the sequences of a
+ *          batch are coupled); G = 1 decodes every sequence as the reference would alone.
+ * Per cell (b,s) and time t: delta (fp32), psi, dur (ints).  Every fl() is one fp32 rounding.
+ *   t = 0   delta = fl(e[b,0,s] - fl32(log S)), dur = 1.
+ *   t >= 1  over the group's previous row:  dmax1[s] = max_b dur[b,t-1,s] + 1,
+ *           dmin[s] = min_b dur[b,t-1,s];
+ *           pen_self[s] = fl(fl32(-w) * fl32(dmax1[s] - max_duration))  if dmax1[s] > max_duration
+ *           pen_from[p] = fl(fl32(-w) * fl32(min_duration - dmin[p]))   if dmin[p] < min_duration
+ *           (an absent penalty is not added); candidates in ascending p:
+ *             p == s: fl(fl(delta[b,t-1,s] + e[b,t,s]) + pen_self[s]),         dur' = dur[b,t-1,s] + 1
+ *             p != s: fl(fl(fl(delta[b,t-1,p] + log_T[p,s]) + e[b,t,s]) + pen_from[p]),  dur' = 1
+ *           a candidate wins only if strictly greater than the best so far, which starts at
+ *           -inf: the first index wins a tie, and a cell whose candidates are all -inf keeps
+ *           delta = -inf, psi = 0, dur = 0 (that 0 enters the next step's dmin).
+ *   end     states[b,T-1] = the first argmax of delta[b,T-1,:], final_score[b] its value;
+ *           states[b,t] = psi[b,t+1,states[b,t+1]].
+ *   log_delta, durations  (B,T,S) or NULL: the whole trellis, written only when given.
+ *   workspace >= hmm355_dchmm_workspace_bytes(B, T, S), 16-byte aligned: psi, one byte per cell.
+ * Limits: 1 <= S <= HMM355_DCHMM_MAX_STATES and group * S <= HMM355_DCHMM_MAX_CELLS (else
+ * HMM355_E_STATES: the rows of a group live in one workgroup's LDS), T >= 1 (else
+ * HMM355_E_SHAPE), B >= 1 and 1 <= group <= B (else HMM355_E_ARG); the size query returns 0 for
+ * a rejected B, T or S.  Every check comes before any launch.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_DCHMM_MAX_STATES 256
+#define HMM355_DCHMM_MAX_CELLS 4096
+size_t hmm355_dchmm_workspace_bytes(int B, int T, int S);
+int hmm355_dchmm_viterbi_f32(const float* emis, const float* log_T, int B, int T, int S, int group,
+                             int min_duration, int max_duration, float penalty_weight,
+                             int64_t* states, float* final_score,
+                             float* log_delta /* (B,T,S) or NULL */, int32_t* durations /* (B,T,S) or NULL */,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 Drop-in for the hot path of crlotwhite/pytorch_hmm: HMMPyTorch.forward_backward /
 viterbi_decode / compute_likelihood, HMMLayer, GaussianHMMLayer,
 MixtureGaussianHMMLayer and HSMMLayer, and the next rows of that path (NeuralHMM,
-SemiMarkovHMM, StreamingHMMProcessor), with the per-time-step loops replaced by
+SemiMarkovHMM, StreamingHMMProcessor, DurationConstrainedHMM), with the per-time-step loops replaced by
 hand-written HIP kernels (csrc/) behind the C ABI in include/hmm355.h and the
 torch.library ops in ops.py.  Tensors must be on a ROCm GPU; there is no CPU path.
 """
@@ -28,3 +28,8 @@ from . import alignment
 from .alignment import ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner
 
 __all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner", "CTCAligner", "CTCSegmentationAligner"]
+
+from .hsmm import DurationConstrainedHMM
+from .utils import compute_state_durations, create_duration_constrained_matrix
+
+__all__ += ["DurationConstrainedHMM", "compute_state_durations", "create_duration_constrained_matrix"]

@@ -31,6 +31,8 @@ DTW_SYMMETRIC, DTW_ASYMMETRIC, DTW_RABINER_JUANG = 0, 1, 2  # HMM355_DTW_* step 
 DTW_PATH = 0x1  # HMM355_DTW_PATH
 CTC_ALPHA, CTC_BETA, CTC_VITERBI = 0x1, 0x2, 0x4  # HMM355_CTC_* flags
 CTC_MAX_TARGET = 2048  # HMM355_CTC_MAX_TARGET
+DCHMM_MAX_STATES = 256  # HMM355_DCHMM_MAX_STATES
+DCHMM_MAX_CELLS = 4096  # HMM355_DCHMM_MAX_CELLS: group size times states
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -54,6 +56,7 @@ EXPORTS = (
     "hmm355_fb_wide_workspace_bytes", "hmm355_forward_backward_wide_f32",
     "hmm355_dtw_workspace_bytes", "hmm355_dtw_f32", "hmm355_softdtw_f32", "hmm355_softdtw_grad_f32",
     "hmm355_ctc_workspace_bytes", "hmm355_ctc_f32", "hmm355_ctc_grad_f32",
+    "hmm355_dchmm_workspace_bytes", "hmm355_dchmm_viterbi_f32",
 )
 
 _lib = None
@@ -148,6 +151,9 @@ def lib():
     L.hmm355_ctc_workspace_bytes.argtypes, L.hmm355_ctc_workspace_bytes.restype = [I, I, I, U], S
     L.hmm355_ctc_f32.argtypes, L.hmm355_ctc_f32.restype = [P, P, P, P, I, I, I, I, I, U, P, P, P, P, P, P, S, P], I
     L.hmm355_ctc_grad_f32.argtypes, L.hmm355_ctc_grad_f32.restype = [P, P, P, P, P, P, I, I, I, I, I, P, P, P], I
+    L.hmm355_dchmm_workspace_bytes.argtypes, L.hmm355_dchmm_workspace_bytes.restype = [I, I, I], S
+    L.hmm355_dchmm_viterbi_f32.argtypes = [P, P, I, I, I, I, I, I, F, P, P, P, P, P, S, P]
+    L.hmm355_dchmm_viterbi_f32.restype = I
     _lib = L
     return L
 

@@ -1,4 +1,5 @@
-"""HSMMLayer — drop-in for the reference's explicit-duration HMM layer (hsmm.py:20-470).
+"""HSMMLayer — drop-in for the reference's explicit-duration HMM layer (hsmm.py:20-470) — and
+DurationConstrainedHMM (hsmm.py:475-590), at the end of this file.
 
 Parameters keep the reference's names, shapes and initialisation (``transition_logits``,
 ``observation_means``, ``observation_log_vars``, ``duration_shape``/``duration_rate``
@@ -20,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._native import DCHMM_MAX_STATES
 from .autograd import GmmLogProb, needs_grad
 
 
@@ -143,3 +145,54 @@ class HSMMLayer(nn.Module):
                 "duration_distribution": self.duration_distribution, "max_duration": self.max_duration,
                 "min_duration": self.min_duration, "expected_durations": self.get_expected_durations().tolist(),
                 "total_parameters": total, "trainable_parameters": trainable}
+
+
+class DurationConstrainedHMM(nn.Module):
+    """Drop-in for the reference's DurationConstrainedHMM (hsmm.py:475-590): an HMM decoder whose
+    Viterbi pass tracks how long each path has stayed in its state and subtracts
+    ``duration_penalty_weight`` per frame for a self-loop past ``max_duration`` and for leaving a
+    state before ``min_duration`` (soft constraints).
+
+    Parameters keep the reference's names, shapes and creation order (``transition_logits``, then
+    ``emission_net`` = Linear(feature_dim, 128), ReLU, Linear(128, num_states), LogSoftmax), so
+    the same seed gives the same initial parameters and the reference's ``state_dict`` loads.
+    The emission network and the transition log-softmax run in torch on the GPU; the recursion
+    (the reference's Python loops over t, s and prev_s) runs in one HIP launch
+    (ops.duration_constrained_viterbi, csrc/dchmm.hip) and decodes the reference's states given
+    the same emission log-probs.
+
+    The reference takes the run lengths that decide a step's penalties as .max() / .min() over
+    the whole batch, so a sequence's decode depends on what it is batched with.  That is kept
+    (the batch then runs in one workgroup: B * num_states <= 4096).  ``per_sequence=True`` is an
+    extension: every sequence gets the penalties of its own run lengths, i.e. what the
+    reference returns when called on one sequence at a time, with no limit on B.
+    """
+
+    def __init__(self, num_states: int, feature_dim: int, min_duration: int = 3, max_duration: int = 30, *,
+                 per_sequence: bool = False):
+        super().__init__()
+        if not 1 <= num_states <= DCHMM_MAX_STATES:
+            raise ValueError(f"DurationConstrainedHMM on gfx950 supports 1 <= num_states <= "
+                             f"{DCHMM_MAX_STATES}, got {num_states}")
+        self.num_states = num_states
+        self.feature_dim = feature_dim
+        self.min_duration = min_duration
+        self.max_duration = max_duration
+        self.per_sequence = bool(per_sequence)
+        self.transition_logits = nn.Parameter(torch.randn(num_states, num_states) * 0.1)
+        self.emission_net = nn.Sequential(nn.Linear(feature_dim, 128), nn.ReLU(), nn.Linear(128, num_states),
+                                          nn.LogSoftmax(dim=-1))
+        self.duration_penalty_weight = 0.1
+
+    def forward(self, observations: torch.Tensor) -> torch.Tensor:
+        """(B,T,D) observations -> (B,T) int64 decoded states."""
+        emission_log_probs = self.emission_net(observations)
+        log_transitions = torch.log(F.softmax(self.transition_logits, dim=-1) + 1e-8)
+        return self._constrained_viterbi(emission_log_probs, log_transitions)
+
+    def _constrained_viterbi(self, emission_log_probs: torch.Tensor, log_transitions: torch.Tensor) -> torch.Tensor:
+        """(B,T,S) emission log-probs and (S,S) log-transitions -> (B,T) int64 states."""
+        states, _, _, _ = ops.duration_constrained_viterbi(
+            emission_log_probs, log_transitions, self.min_duration, self.max_duration,
+            self.duration_penalty_weight, self.per_sequence)
+        return states

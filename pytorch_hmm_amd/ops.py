@@ -21,6 +21,9 @@ shape-only fake implementations; their only real implementation is the HIP libra
       -> (loglik, alpha, beta, path, score)
   torch.ops.hmm355.ctc_grad(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes,
                             blank, want_gamma) -> (grad, gamma)
+  torch.ops.hmm355.duration_constrained_viterbi(emission_log_probs, log_transitions, min_duration,
+                                                max_duration, penalty_weight, per_sequence, want_trellis)
+      -> (states, final_score, log_delta, durations)
 """
 from typing import Optional, Tuple
 
@@ -845,3 +848,59 @@ def _(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes, 
     B, T, S = alpha.shape
     return (alpha.new_empty((T, B, num_classes), dtype=torch.float32),
             alpha.new_empty((B, T, S) if want_gamma else _EMPTY, dtype=torch.float32))
+
+
+# ------------------------------------------------------------------ duration-constrained Viterbi
+@torch.library.custom_op("hmm355::duration_constrained_viterbi", mutates_args=())
+def duration_constrained_viterbi(emission_log_probs: Tensor, log_transitions: Tensor, min_duration: int,
+                                 max_duration: int, penalty_weight: float = 0.1, per_sequence: bool = False,
+                                 want_trellis: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The duration-penalty Viterbi of DurationConstrainedHMM (hmm355_dchmm_viterbi_f32,
+    csrc/dchmm.hip; the recursion is spelled out in include/hmm355.h).  emission_log_probs (B,T,S),
+    log_transitions (S,S).  Returns (states (B,T) int64; final_score (B) = max_s delta[b,T-1,s];
+    log_delta (B,T,S) fp32 and durations (B,T,S) int32, the whole trellis, or two empty tensors
+    without want_trellis).  As in the reference the penalties of a step come from the largest and
+    smallest run length over the whole batch, so the sequences of a batch are coupled and the
+    batch runs in one workgroup: B * S <= 4096.  per_sequence=True gives every sequence its own
+    penalties (the reference run on one sequence at a time), one workgroup each and any B.
+    1 <= S <= 256.  Sizes outside the limits raise ValueError."""
+    nat.require_gpu(emission_log_probs, log_transitions)
+    if emission_log_probs.dim() != 3:
+        raise ValueError(f"emission_log_probs must be (B, T, S); got {tuple(emission_log_probs.shape)}")
+    B, T, S = emission_log_probs.shape
+    if tuple(log_transitions.shape) != (S, S):
+        raise ValueError(f"log_transitions must be ({S}, {S}); got {tuple(log_transitions.shape)}")
+    if B < 1 or T < 1:
+        raise ValueError(f"emission_log_probs needs B >= 1 and T >= 1; got {tuple(emission_log_probs.shape)}")
+    if not 1 <= S <= nat.DCHMM_MAX_STATES:
+        raise ValueError(f"duration_constrained_viterbi supports 1 <= S <= {nat.DCHMM_MAX_STATES} states; got {S}")
+    group = 1 if per_sequence else B
+    if group * S > nat.DCHMM_MAX_CELLS:
+        raise ValueError(
+            f"duration_constrained_viterbi couples the batch (the penalties of a step are taken over all B "
+            f"sequences), which needs B * S <= {nat.DCHMM_MAX_CELLS}; got B = {B}, S = {S}.  per_sequence=True "
+            "decodes each sequence with its own penalties at any B")
+    dev = emission_log_probs.device
+    e, lT = _f32c(emission_log_probs.detach()), _f32c(log_transitions.detach())
+    states = torch.empty((B, T), dtype=torch.int64, device=dev)
+    score = torch.empty(B, device=dev)
+    delta = torch.empty((B, T, S) if want_trellis else _EMPTY, device=dev)
+    dur = torch.empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.int32, device=dev)
+    L = nat.lib()
+    ws = _workspace(L.hmm355_dchmm_workspace_bytes(B, T, S), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_dchmm_viterbi_f32(
+            nat.ptr(e), nat.ptr(lT), B, T, S, group, int(min_duration), int(max_duration), float(penalty_weight),
+            nat.ptr(states), nat.ptr(score), nat.ptr(delta) if want_trellis else None,
+            nat.ptr(dur) if want_trellis else None, nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return states, score, delta, dur
+
+
+@duration_constrained_viterbi.register_fake
+def _(emission_log_probs, log_transitions, min_duration, max_duration, penalty_weight=0.1, per_sequence=False,
+      want_trellis=False):
+    B, T, S = emission_log_probs.shape
+    return (emission_log_probs.new_empty((B, T), dtype=torch.int64),
+            emission_log_probs.new_empty(B, dtype=torch.float32),
+            emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.float32),
+            emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.int32))
