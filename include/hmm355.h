@@ -37,7 +37,7 @@ extern "C" {
 #define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
-#define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024]                  */
+#define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
 
 /* Emission encodings accepted by the recursions. */
 #define HMM355_OBS_PROB 0   /* x is a probability: the kernel uses log(x + 1e-8) / x + 1e-8 (hmm.py:86,152) */
@@ -295,6 +295,66 @@ size_t hmm355_hsmm_workspace_bytes_ex(int B, int T, int S, int Dmax, unsigned fl
 int hmm355_hsmm_viterbi_ex_f32(const float* lp, const float* dur_lp, const float* log_T, int B,
                                int T, int S, int Dmax, unsigned flags, int64_t* states,
                                float* scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * HSMM forward-backward (csrc/hsmm_fb.hip): the sum over the segmentations that
+ * hmm355_hsmm_viterbi_f32 maximises over.  Log-likelihood, state posteriors and the expected
+ * counts, each the derivative of loglik with respect to the matching input.  The reference has
+ * no such routine (HSMMLayer can only decode, hsmm.py:208-354).
+ *   lp (B,T,S) frame log-scores; dur_lp (S,Dmax), column d-1 scores duration d; log_T (S,S);
+ *   log_init (S) or NULL = all zeros (what the decoder uses).  -inf entries are allowed, +inf
+ *   and NaN are not.
+ * A segmentation (s_1,d_1)..(s_K,d_K) has sum d_k = T exactly (the last segment ends at frame
+ * T-1: no censoring), 1 <= d_k <= Dmax and s_k != s_k+1: log_T's diagonal is never used.  Its
+ * score is sum_k dur_lp[s_k,d_k-1] + (lp over its frames) + (k = 1 ? log_init[s_1] :
+ * log_T[s_k-1,s_k]).  With O(a..t,s) the sum of lp[.,s] over frames a..t:
+ *   begin_0(s) = log_init(s);  F_t(s) = LSE_{d <= min(Dmax,t+1)} begin_t-d+1(s) + O(t-d+1..t,s)
+ *   + dur_lp[s,d-1];  begin_t+1(s) = LSE_{s' != s} F_t(s') + log_T[s',s];
+ *   Bend_T-1(s) = 0;  Bend_t(s) = LSE_{s' != s} log_T[s,s'] + Bbeg_t+1(s');
+ *   Bbeg_t(s) = LSE_{d <= min(Dmax,T-t)} dur_lp[s,d-1] + O(t..t+d-1,s) + Bend_t+d-1(s).
+ * Every LSE takes its own maximum (exact whatever the spread of its candidates); -inf candidates
+ * drop out and a cell without a finite candidate is -inf.  The recursions run on lp[t,.] minus
+ * its row maximum (0 for a row without a finite one), which every segmentation pays once per
+ * frame; the sum of the maxima is carried in fp64 and added to loglik.
+ *   loglik (B)             = LSE_s F_T-1(s).  Always produced.
+ *   gamma (B,T,S)          = P(state at frame t is s) = sum_{a<=t} P(segment of s begins at a) -
+ *                            sum_{e<t} P(segment of s ends at e), an fp64 running sum, with
+ *                            P(begin) = exp(begin + Bbeg - loglik), P(end) = exp(F + Bend - loglik)
+ *   dur_counts (B,S,Dmax)  = expected number of (s,d) segments
+ *   trans_counts (B,S,S)   = expected number of i -> j transitions (zero diagonal)
+ *   init_post (B,S)        = exp(log_init + Bbeg_0 - loglik)
+ * sum dur_counts = sum trans_counts + 1.  A sequence without a segmentation has loglik = -inf
+ * and every posterior and count 0; no NaN is written and its neighbours are unaffected.  No
+ * floating-point atomics: two calls on the same inputs return the same bits.
+ *   flags  HMM355_HSMM_FB_GAMMA / _DUR / _TRANS / _INIT select the optional outputs (their
+ *          pointers may be NULL otherwise).  With none of them only the forward sum runs and no
+ *          (B,T,S) table is written.  HMM355_FORM_GENERAL is accepted (there is one form).
+ *   workspace >= hmm355_hsmm_fb_workspace_bytes(B,T,S,Dmax,flags), 16-byte aligned: log_T in both
+ *          orientations, the row maxima, and with any output flag begin | F | Bend | Bbeg (B,T,S)
+ *          fp32 of the shifted scores; with _DUR fp64 prefix sums of the shifted scores and
+ *          -inf counts (B,T,S); with _DUR / _TRANS the partial sums of the counts.
+ * 1 <= S <= HMM355_HSMM_FB_MAX_STATES (else HMM355_E_STATES); 1 <= Dmax <=
+ * HMM355_HSMM_FB_MAX_DURATION and S * Dmax <= HMM355_HSMM_FB_MAX_CELLS (else HMM355_E_DURATION:
+ * a sequence's open segments live in 64 KiB of one workgroup's LDS); T >= 1, 0 <= B <=
+ * HMM355_HSMM_FB_MAX_BATCH (a sequence is a grid row) and B * T <= 2^31 (else HMM355_E_SHAPE: call
+ * in batch slices); B == 0 is a no-op.  The size query returns 0 for a rejected shape or
+ * flag.  Every check comes before any launch.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_HSMM_FB_GAMMA 0x10u
+#define HMM355_HSMM_FB_DUR 0x20u
+#define HMM355_HSMM_FB_TRANS 0x40u
+#define HMM355_HSMM_FB_INIT 0x80u
+#define HMM355_HSMM_FB_MAX_STATES 256
+#define HMM355_HSMM_FB_MAX_DURATION 128
+#define HMM355_HSMM_FB_MAX_CELLS 16384
+#define HMM355_HSMM_FB_MAX_BATCH 65535
+size_t hmm355_hsmm_fb_workspace_bytes(int B, int T, int S, int Dmax, unsigned flags);
+int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const float* log_T,
+                       const float* log_init /* (S) or NULL */, int B, int T, int S, int Dmax,
+                       unsigned flags, float* loglik, float* gamma /* (B,T,S) or NULL */,
+                       float* dur_counts /* (B,S,Dmax) or NULL */,
+                       float* trans_counts /* (B,S,S) or NULL */, float* init_post /* (B,S) or NULL */,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Recursions with one transition matrix per time step (NeuralHMM).  Replace

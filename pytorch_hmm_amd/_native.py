@@ -33,6 +33,11 @@ CTC_ALPHA, CTC_BETA, CTC_VITERBI = 0x1, 0x2, 0x4  # HMM355_CTC_* flags
 CTC_MAX_TARGET = 2048  # HMM355_CTC_MAX_TARGET
 DCHMM_MAX_STATES = 256  # HMM355_DCHMM_MAX_STATES
 DCHMM_MAX_CELLS = 4096  # HMM355_DCHMM_MAX_CELLS: group size times states
+HSMM_FB_GAMMA, HSMM_FB_DUR, HSMM_FB_TRANS, HSMM_FB_INIT = 0x10, 0x20, 0x40, 0x80  # HMM355_HSMM_FB_* flags
+HSMM_FB_MAX_STATES = 256  # HMM355_HSMM_FB_MAX_STATES
+HSMM_FB_MAX_DURATION = 128  # HMM355_HSMM_FB_MAX_DURATION
+HSMM_FB_MAX_CELLS = 16384  # HMM355_HSMM_FB_MAX_CELLS: states times max_duration
+HSMM_FB_MAX_BATCH = 65535  # HMM355_HSMM_FB_MAX_BATCH: sequences per native call
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -42,7 +47,7 @@ EXPORTS = (
     "hmm355_viterbi_workspace_bytes", "hmm355_viterbi_workspace_bytes_ex", "hmm355_viterbi_f32",
     "hmm355_gmm_workspace_bytes", "hmm355_gmm_diag_logprob_f32",
     "hmm355_hsmm_workspace_bytes", "hmm355_hsmm_viterbi_f32", "hmm355_hsmm_workspace_bytes_ex",
-    "hmm355_hsmm_viterbi_ex_f32",
+    "hmm355_hsmm_viterbi_ex_f32", "hmm355_hsmm_fb_workspace_bytes", "hmm355_hsmm_fb_f32",
     "hmm355_tv_fb_workspace_bytes", "hmm355_tv_forward_backward_f32", "hmm355_tv_forward_backward_ex_f32",
     "hmm355_tv_viterbi_workspace_bytes", "hmm355_tv_viterbi_f32",
     "hmm355_semimarkov_workspace_bytes", "hmm355_semimarkov_quad_f32",
@@ -98,6 +103,9 @@ def lib():
     L.hmm355_hsmm_workspace_bytes_ex.argtypes, L.hmm355_hsmm_workspace_bytes_ex.restype = [I, I, I, I, U], S
     L.hmm355_hsmm_viterbi_ex_f32.argtypes = [P, P, P, I, I, I, I, U, P, P, P, S, P]
     L.hmm355_hsmm_viterbi_ex_f32.restype = I
+    L.hmm355_hsmm_fb_workspace_bytes.argtypes, L.hmm355_hsmm_fb_workspace_bytes.restype = [I, I, I, I, U], S
+    L.hmm355_hsmm_fb_f32.argtypes = [P, P, P, P, I, I, I, I, U, P, P, P, P, P, P, S, P]
+    L.hmm355_hsmm_fb_f32.restype = I
     LL = ctypes.c_longlong
     L.hmm355_tv_fb_workspace_bytes.argtypes, L.hmm355_tv_fb_workspace_bytes.restype = [I, I, I], S
     L.hmm355_tv_forward_backward_f32.argtypes = [P, P, LL, LL, P, I, I, I, U, P, P, P, P, P, P, S, P]

@@ -589,3 +589,49 @@ class CTCLogLik(torch.autograd.Function):
         grad, _ = ops.ctc_grad(alpha, beta, loglik, targets, il, tl, ctx.classes, ctx.blank)
         grad = grad * grad_loglik.to(grad.dtype)[None, :, None]
         return grad.to(ctx.dtype), None, None, None, None
+
+
+class HsmmLogLik(torch.autograd.Function):
+    """loglik (B) = log of the sum over segmentations of the explicit-duration model
+    (ops.hsmm_forward_backward, csrc/hsmm_fb.hip), differentiable in lp (B,T,S), dur_lp (S,Dmax),
+    log_T (S,S) and log_init (S) or None.  The forward is the forward sum alone; the backward is
+    one forward-backward call that forms only the posteriors and counts of the inputs that need a
+    gradient, weighted per sequence by the incoming gradient:
+
+        grad_lp = g_b gamma_b            grad_dur_lp   = sum_b g_b dur_counts_b
+        grad_log_T = sum_b g_b trans_counts_b          grad_log_init = sum_b g_b init_post_b
+
+    log_T's diagonal is never used by the model, so its gradient is zero there.
+    The backward's call runs the forward sum again beside the backward one: no (B,T,S) table is
+    kept alive between forward and backward.
+
+        loglik = HsmmLogLik.apply(lp, dur_lp, log_T, log_init)
+    """
+
+    @staticmethod
+    def forward(ctx, lp, dur_lp, log_T, log_init=None):
+        from . import ops
+        saved = [t.detach() for t in (lp, dur_lp, log_T)]
+        saved.append(None if log_init is None else log_init.detach())
+        loglik = ops.hsmm_forward_backward(*saved)[0]
+        ctx.save_for_backward(*saved)
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (lp, dur_lp, log_T, log_init))
+        return loglik
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        lp, dur_lp, log_T, log_init = ctx.saved_tensors
+        need = list(ctx.needs_input_grad[:4])
+        need[3] = need[3] and log_init is not None
+        if not any(need):
+            return None, None, None, None
+        _, gamma, dur_c, trans_c, init_p = ops.hsmm_forward_backward(
+            lp, dur_lp, log_T, log_init, want_gamma=need[0], want_dur=need[1], want_trans=need[2],
+            want_init=need[3])
+        g = g.to(torch.float32)
+        grads = [gamma * g[:, None, None] if need[0] else None,
+                 torch.einsum("b,bsd->sd", g, dur_c) if need[1] else None,
+                 torch.einsum("b,bij->ij", g, trans_c) if need[2] else None,
+                 torch.einsum("b,bs->s", g, init_p) if need[3] else None]
+        return tuple(None if x is None else x.to(dt) for x, dt in zip(grads, ctx.dtypes))

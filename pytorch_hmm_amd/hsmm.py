@@ -11,6 +11,10 @@ observation scores run in the gfx950 GMM scorer (one component) and the segment 
 same tables at every supported size: the segment sums follow torch.sum's CPU cascade order
 (csrc/tsum.h), pinned to torch.sum for every length 1..1024 and to a reference fixture with
 83- and 82-frame segments (tests/golden/hsmm_d96.npz).
+
+``log_likelihood``, ``state_posteriors`` and ``compute_loss`` are additions (the reference's layer
+can only decode): the sum over the decoder's segmentations and its gradients, on the same
+tables (csrc/hsmm_fb.hip, autograd.HsmmLogLik).
 """
 import math
 import warnings
@@ -22,7 +26,8 @@ import torch.nn.functional as F
 
 from . import ops
 from ._native import DCHMM_MAX_STATES
-from .autograd import GmmLogProb, needs_grad
+from ._native import require_gpu as nat_require_gpu
+from .autograd import GmmLogProb, HsmmLogLik, needs_grad
 
 
 class HSMMLayer(nn.Module):
@@ -126,6 +131,41 @@ class HSMMLayer(nn.Module):
 
     def forward(self, observations: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.viterbi_decode_hsmm(observations)
+
+    # -- likelihood, posteriors, training loss (csrc/hsmm_fb.hip; not in the reference) -------
+    def _segment_tables(self, observations: torch.Tensor):
+        """The decoder's tables (viterbi_decode_hsmm), built under the caller's grad mode."""
+        S, Dm = self.num_states, self.max_duration
+        if not ops.hsmm_fb_supported(S, Dm):
+            raise ValueError(
+                f"HSMMLayer's likelihood and posteriors on gfx950 support num_states <= "
+                f"{ops.HSMM_FB_MAX_STATES}, max_duration <= {ops.HSMM_FB_MAX_DURATION} and num_states * "
+                f"max_duration <= {ops.HSMM_FB_MAX_CELLS}; got {S} and {Dm}")
+        nat_require_gpu(observations)
+        obs_log_probs = self.get_observation_log_probs(observations)
+        dur_lp = torch.log(self.get_duration_probabilities() + self.eps)
+        log_T = torch.log(self.get_transition_matrix() + self.eps)
+        if dur_lp.shape[1] < Dm:
+            raise IndexError(f"index {dur_lp.shape[1]} is out of bounds for dimension 1 with size {dur_lp.shape[1]}")
+        return obs_log_probs, dur_lp[:, :Dm], log_T
+
+    def log_likelihood(self, observations: torch.Tensor) -> torch.Tensor:
+        """(B,T,D) -> (B,) log of the sum over all segmentations of the score viterbi_decode_hsmm
+        maximises; differentiable in every parameter and in the observations."""
+        lp, dur_lp, log_T = self._segment_tables(observations)
+        if needs_grad(lp, dur_lp, log_T):
+            return HsmmLogLik.apply(lp, dur_lp, log_T, None)
+        return ops.hsmm_forward_backward(lp, dur_lp, log_T)[0]
+
+    def state_posteriors(self, observations: torch.Tensor) -> torch.Tensor:
+        """(B,T,D) -> (B,T,S) P(state at frame t is s | observations); rows sum to 1."""
+        with torch.no_grad():
+            lp, dur_lp, log_T = self._segment_tables(observations)
+            return ops.hsmm_forward_backward(lp, dur_lp, log_T, want_gamma=True)[1]
+
+    def compute_loss(self, observations: torch.Tensor) -> torch.Tensor:
+        """Mean negative log-likelihood (as GaussianHMMLayer.compute_loss)."""
+        return -self.log_likelihood(observations).mean()
 
     def get_expected_durations(self) -> torch.Tensor:
         if self.duration_distribution == "gamma":

@@ -10,6 +10,9 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.viterbi(obs, log_P, init, obs_mode) -> (states, log_delta, final_score)
   torch.ops.hmm355.gmm_diag_logprob(x, means, log_vars, log_w, mix_lse) -> log_probs
   torch.ops.hmm355.hsmm_viterbi(lp, dur_lp, log_T) -> (states, scores)
+  torch.ops.hmm355.hsmm_forward_backward(lp, dur_lp, log_T, log_init, want_gamma=, want_dur=,
+                                         want_trans=, want_init=, flags=)
+      -> (loglik, gamma, dur_counts, trans_counts, init_post)
   torch.ops.hmm355.tv_forward_backward(log_obs, log_A, log_p0, out_mask)
       -> (posterior, forward, backward, loglik, lik_ref)
   torch.ops.hmm355.tv_viterbi(log_obs, log_A, init) -> (states, log_delta)
@@ -337,6 +340,77 @@ def _ws_batch(ws_bytes, B, T, S, Dm, dev, what):
 def _(lp, dur_lp, log_T, flags=0):
     B, T, S = lp.shape
     return lp.new_empty((B, T), dtype=torch.int64), lp.new_empty(B)
+
+
+HSMM_FB_MAX_STATES = nat.HSMM_FB_MAX_STATES
+HSMM_FB_MAX_DURATION = nat.HSMM_FB_MAX_DURATION
+HSMM_FB_MAX_CELLS = nat.HSMM_FB_MAX_CELLS
+
+
+def hsmm_fb_supported(S: int, Dm: int) -> bool:
+    """The sizes hsmm_forward_backward takes (csrc/hsmm_fb.hip: a sequence's open segments live in
+    64 KiB of LDS)."""
+    return 1 <= S <= HSMM_FB_MAX_STATES and 1 <= Dm <= HSMM_FB_MAX_DURATION and S * Dm <= HSMM_FB_MAX_CELLS
+
+
+@torch.library.custom_op("hmm355::hsmm_forward_backward", mutates_args=())
+def hsmm_forward_backward(lp: Tensor, dur_lp: Tensor, log_T: Tensor, log_init: Optional[Tensor] = None, *,
+                          want_gamma: bool = False, want_dur: bool = False, want_trans: bool = False,
+                          want_init: bool = False, flags: int = 0
+                          ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The sum over the segmentations hsmm_viterbi maximises over (hmm355_hsmm_fb_f32,
+    csrc/hsmm_fb.hip) -> (loglik (B), gamma (B,T,S), dur_counts (B,S,Dmax), trans_counts (B,S,S),
+    init_post (B,S)); an output that is not wanted comes back as an empty (0,) tensor.  Each output
+    is the derivative of loglik with respect to lp, dur_lp, log_T and log_init.  log_init None:
+    all zeros, as in the decoder.  With no output wanted only the forward sum runs."""
+    nat.require_gpu(lp, dur_lp, log_T, log_init)
+    lp, dur_lp, log_T = _f32c(lp), _f32c(dur_lp), _f32c(log_T)
+    if log_init is not None:
+        log_init = _f32c(log_init)
+    B, T, S = lp.shape
+    Dm = dur_lp.shape[1]
+    if dur_lp.shape[0] != S or tuple(log_T.shape) != (S, S) or (log_init is not None and log_init.shape != (S,)):
+        raise ValueError(f"hsmm_forward_backward: lp {tuple(lp.shape)}, dur_lp {tuple(dur_lp.shape)}, log_T "
+                         f"{tuple(log_T.shape)} and log_init do not agree on the number of states")
+    dev = lp.device
+    loglik = torch.empty(B, device=dev)
+    gamma = torch.empty((B, T, S) if want_gamma else _EMPTY, device=dev)
+    dur_counts = torch.empty((B, S, Dm) if want_dur else _EMPTY, device=dev)
+    trans_counts = torch.empty((B, S, S) if want_trans else _EMPTY, device=dev)
+    init_post = torch.empty((B, S) if want_init else _EMPTY, device=dev)
+    L = nat.lib()
+    fl = (int(flags) | (nat.HSMM_FB_GAMMA if want_gamma else 0) | (nat.HSMM_FB_DUR if want_dur else 0) |
+          (nat.HSMM_FB_TRANS if want_trans else 0) | (nat.HSMM_FB_INIT if want_init else 0))
+    if B == 0 or T < 1 or not hsmm_fb_supported(S, Dm):
+        # the native call names what is wrong with the shape (nothing is launched)
+        nat.check(L.hmm355_hsmm_fb_f32(None, None, None, None, B, T, S, Dm, fl, None, None, None, None, None,
+                                       None, 0, None))
+        return loglik, gamma, dur_counts, trans_counts, init_post
+    wsb = lambda b_, t_, s_, d_: L.hmm355_hsmm_fb_workspace_bytes(b_, t_, s_, d_, fl)
+    Bc = _ws_batch(wsb, B, T, S, Dm, dev, "HSMM forward-backward")
+    Bc = max(1, min(Bc, nat.HSMM_FB_MAX_BATCH, (1 << 31) // T))  # the native call's limits on B and B * T
+    ws = _workspace(wsb(Bc, T, S, Dm), dev)
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, Bc):
+            nb = min(Bc, B - b0)
+            nat.check(L.hmm355_hsmm_fb_f32(
+                nat.ptr(lp[b0:b0 + nb]), nat.ptr(dur_lp), nat.ptr(log_T), nat.ptr(log_init), nb, T, S, Dm, fl,
+                nat.ptr(loglik[b0:b0 + nb]), nat.ptr(gamma[b0:b0 + nb]) if want_gamma else None,
+                nat.ptr(dur_counts[b0:b0 + nb]) if want_dur else None,
+                nat.ptr(trans_counts[b0:b0 + nb]) if want_trans else None,
+                nat.ptr(init_post[b0:b0 + nb]) if want_init else None, nat.ptr(ws), ws.numel(),
+                nat.stream_of(dev)))
+    return loglik, gamma, dur_counts, trans_counts, init_post
+
+
+@hsmm_forward_backward.register_fake
+def _(lp, dur_lp, log_T, log_init=None, *, want_gamma=False, want_dur=False, want_trans=False, want_init=False,
+      flags=0):
+    B, T, S = lp.shape
+    Dm = dur_lp.shape[1]
+    return (lp.new_empty(B), lp.new_empty((B, T, S) if want_gamma else _EMPTY),
+            lp.new_empty((B, S, Dm) if want_dur else _EMPTY), lp.new_empty((B, S, S) if want_trans else _EMPTY),
+            lp.new_empty((B, S) if want_init else _EMPTY))
 
 
 # ------------------------------------------------- time-varying transitions (NeuralHMM)
