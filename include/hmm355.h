@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -637,6 +637,89 @@ int hmm355_dchmm_viterbi_f32(const float* emis, const float* log_T, int B, int T
                              int64_t* states, float* final_score,
                              float* log_delta /* (B,T,S) or NULL */, int32_t* durations /* (B,T,S) or NULL */,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Transcript forced alignment (csrc/forced.hip): every sequence has its own left-to-right chain
+ * of S_b positions (the states of its transcript, in order); a position stays, advances by one
+ * or skips one; a path starts in position 0 and ends in position S_b - 1.  One launch per call,
+ * one workgroup per sequence and job (forward sum, backward sum, Viterbi).
+ *   log_probs (B,T,C) fp32 row-major, batch first; -inf entries are allowed, +inf and NaN are not
+ *   state_ids (B,Smax) int32: the class (column of log_probs) of each position; only the first
+ *             state_lengths[b] of row b are read.  An id outside [0, C) is never used as an
+ *             index: its emission counts as -inf.  NULL: id_s = s (log_probs is already
+ *             (B,T,S): monotonic alignment search); needs C >= Smax, else HMM355_E_ARG
+ *   input_lengths, state_lengths  (B) int32 device arrays.  The caller guarantees
+ *             1 <= input_lengths[b] <= T and 1 <= state_lengths[b] <= Smax (the Python layer
+ *             checks them on the host); the kernels clamp what they read to those ranges
+ *   log_stay, log_next, log_skip  (B,Smax) fp32 or NULL: the weights of s -> s, s -> s + 1 and
+ *             s -> s + 2, indexed by the source position; -inf entries are allowed.  NULL means
+ *             0, 0 and -inf (no skips).  With all three and state_ids NULL the step has no
+ *             weight adds and reads its emissions as consecutive floats.
+ * With e[t,s] = log_probs[b,t,id_s]; tables are (B,T,Smax):
+ *   alpha[0,0] = e[0,0], alpha[0,s>0] = -inf,
+ *   alpha[t,s] = e[t,s] + LSE(alpha[t-1,s] + stay[s], alpha[t-1,s-1] + next[s-1],
+ *                             alpha[t-1,s-2] + skip[s-2]);
+ *   beta[T_b-1,S_b-1] = 0, beta[t,s] = LSE(stay[s] + e[t+1,s] + beta[t+1,s],
+ *                next[s] + e[t+1,s+1] + beta[t+1,s+1], skip[s] + e[t+1,s+2] + beta[t+1,s+2])
+ *   (beta leaves its own frame's emission out, as the CTC tables do).  -inf candidates drop out
+ *   of the LSE; frames >= input_lengths[b] and positions >= S_b are -inf.
+ * T, B, C >= 1 (else HMM355_E_ARG); 1 <= Smax <= HMM355_FORCED_MAX_POSITIONS (else
+ * HMM355_E_STATES); a size that overflows returns HMM355_E_SHAPE; the size query returns 0 for any
+ * of them.  Every check comes before any launch.
+ *
+ * hmm355_forced_f32
+ *   loglik (B): alpha[T_b-1, S_b-1]; -inf for a pair with no path (S_b > T_b without skips,
+ *          for example).  Always produced.
+ *   flags  HMM355_FORCED_ALPHA: store alpha.  Without it the forward sum writes no table.
+ *          HMM355_FORCED_BETA: store beta.
+ *          HMM355_FORCED_VITERBI: the best single path, max in place of LSE; candidates in the
+ *            order stay, s-1, s-2 with strict >, so the first wins a tie; each candidate is one
+ *            fp32 add of value and weight, the cell one more add of the emission.  path (B,T)
+ *            int32: the position of each frame, -1 for frames >= input_lengths[b] and in every
+ *            frame of a pair with no path; score (B): alpha's max-plus counterpart at
+ *            [T_b-1, S_b-1] (-inf then); durations (B,Smax) int32: the frames the path spends
+ *            in each position, 0 for a skipped position, one >= S_b and a pair with no path.
+ *   workspace >= hmm355_forced_workspace_bytes(B, T, Smax, flags), 16-byte aligned (with
+ *          HMM355_FORCED_VITERBI the 2-bit choices of every cell; 256 bytes otherwise).
+ * hmm355_forced_grad_f32: from the alpha, beta and loglik of one hmm355_forced_f32 call and the
+ *   same ids, lengths and weights (log_probs itself is not read again: alpha holds its
+ *   emissions), any of (at least one)
+ *   gamma (B,T,Smax): exp(alpha + beta - loglik), 0 where either is -inf.  Every such exponent
+ *     is normalised by its frame's own LSE over s of alpha + beta - loglik (0 in exact
+ *     arithmetic), which cancels the rounding that the frame's fp32 alpha and beta share;
+ *   grad_log_probs (B,T,C) = d loglik / d log_probs: the sum of gamma[b,t,s] over id_s = c;
+ *   grad_stay, grad_next, grad_skip (B,Smax) = d loglik / d log_stay, ...:
+ *     grad_stay[b,s] = sum over 1 <= t < T_b of exp(alpha[t-1,s] + stay[s] + e[t,s] + beta[t,s]
+ *     - loglik), grad_next / grad_skip with e and beta at s + 1 / s + 2 (a NULL weight array
+ *     counts as its default).  Each term is formed as gamma of the target position times the
+ *     transition's share among the candidates into it, which is the same number.
+ *   All are 0 in frames >= input_lengths[b], positions >= S_b and for a pair with no path.  For
+ *   a pair with a path every frame of grad_log_probs sums to 1 and the three transition
+ *   gradients together to T_b - 1.  No atomics: two calls on the same inputs return the same bits.
+ *   workspace: needed for the transition gradients only (else it may be NULL):
+ *     >= hmm355_forced_workspace_bytes(B, T, Smax, HMM355_FORCED_GRAD), 16-byte aligned (the sums
+ *     of every tile of frames, added in tile order by a second launch); HMM355_FORCED_GRAD is a
+ *     flag of the size query alone (together with the others it returns the larger need), and
+ *     hmm355_forced_f32 rejects it.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_FORCED_ALPHA 0x1u
+#define HMM355_FORCED_BETA 0x2u
+#define HMM355_FORCED_VITERBI 0x4u
+#define HMM355_FORCED_GRAD 0x8u
+#define HMM355_FORCED_MAX_POSITIONS 4096
+size_t hmm355_forced_workspace_bytes(int B, int T, int Smax, unsigned flags);
+int hmm355_forced_f32(const float* log_probs, const int* state_ids, const int* input_lengths,
+                      const int* state_lengths, const float* log_stay, const float* log_next,
+                      const float* log_skip, int B, int T, int C, int Smax, unsigned flags,
+                      float* alpha, float* beta, float* loglik, int* path, float* score,
+                      int* durations, void* workspace, size_t workspace_bytes, void* stream);
+int hmm355_forced_grad_f32(const float* alpha, const float* beta, const float* loglik,
+                           const int* state_ids, const int* input_lengths,
+                           const int* state_lengths, const float* log_stay, const float* log_next,
+                           const float* log_skip, int B, int T, int C, int Smax, float* gamma,
+                           float* grad_log_probs, float* grad_stay, float* grad_next,
+                           float* grad_skip, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }

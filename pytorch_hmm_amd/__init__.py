@@ -25,9 +25,13 @@ __all__ += ["HMMLayer", "GaussianHMMLayer", "MixtureGaussianHMMLayer", "HSMMLaye
             "StreamingHMMProcessor", "StreamingResult", "AdaptiveLatencyController"]
 
 from . import alignment
-from .alignment import ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner
+from .alignment import (ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner, ForcedAligner,
+                        forced_align, forced_alignment_loglik, forced_alignment_posteriors,
+                        monotonic_alignment_search)
 
-__all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner", "CTCAligner", "CTCSegmentationAligner"]
+__all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner", "CTCAligner", "CTCSegmentationAligner",
+            "ForcedAligner", "forced_align", "forced_alignment_loglik", "forced_alignment_posteriors",
+            "monotonic_alignment_search"]
 
 from .hsmm import DurationConstrainedHMM
 from .utils import compute_state_durations, create_duration_constrained_matrix

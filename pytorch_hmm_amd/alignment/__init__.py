@@ -15,17 +15,27 @@ alignment it was written to give; ctc_forced_align also returns the expanded pos
 score.  CTCAligner.forward stays the reference's nn.CTCLoss wrapper; decoding, collapsing and
 CTCSegmentationAligner are plain torch on any device.
 
+Transcript forced alignment (forced.py) has no counterpart in the reference: every utterance is
+aligned to its own left-to-right chain of transcript states (stay / next / optional skip, ragged
+in both lengths) in one launch of csrc/forced.hip -- the best path with per-position durations
+(forced_align, monotonic_alignment_search), the differentiable sum over all paths
+(forced_alignment_loglik, autograd.ForcedLogLik), the posteriors, and the ForcedAligner module.
+
 The kernels take tensors on a ROCm GPU only.  Of the reference package's four listed techniques
-(DTW, CTC, attention, monotonic) it implements these two, and so does this package.
+(DTW, CTC, attention, monotonic) it implements the first two; this package adds the monotonic one.
 """
 from .ctc import (CTCAligner, CTCSegmentationAligner, collapse_repeated_tokens, ctc_alignment_path,
                   ctc_backward_algorithm, ctc_decode_sequence, ctc_forced_align, ctc_forward_algorithm,
                   expand_targets_with_blank, remove_ctc_blanks)
 from .dtw import (ConstrainedDTWAligner, DTWAligner, compute_distance_matrix, compute_dtw_path, dtw_alignment,
                   dtw_distance, extract_phoneme_durations, phoneme_audio_alignment)
+from .forced import (ForcedAligner, forced_align, forced_alignment_loglik, forced_alignment_posteriors,
+                     monotonic_alignment_search)
 
 __all__ = ["DTWAligner", "ConstrainedDTWAligner", "compute_distance_matrix", "compute_dtw_path", "dtw_alignment",
            "dtw_distance", "phoneme_audio_alignment", "extract_phoneme_durations",
            "CTCAligner", "CTCSegmentationAligner", "ctc_forward_algorithm", "ctc_backward_algorithm",
            "ctc_alignment_path", "ctc_forced_align", "expand_targets_with_blank", "remove_ctc_blanks",
-           "collapse_repeated_tokens", "ctc_decode_sequence"]
+           "collapse_repeated_tokens", "ctc_decode_sequence",
+           "ForcedAligner", "forced_align", "forced_alignment_loglik", "forced_alignment_posteriors",
+           "monotonic_alignment_search"]

@@ -591,6 +591,52 @@ class CTCLogLik(torch.autograd.Function):
         return grad.to(ctx.dtype), None, None, None, None
 
 
+class ForcedLogLik(torch.autograd.Function):
+    """loglik (B) = the log of the sum over every path of an utterance through its own
+    left-to-right chain (ops.forced, csrc/forced.hip), differentiable in log_probs (B,T,C) and in
+    whichever of log_stay / log_next / log_skip (B,Smax) are given.  The forward keeps alpha and
+    beta; the backward is one launch of the occupancy kernel (ops.forced_grad):
+
+        d loglik[b] / d log_probs[b,t,c] = sum of gamma[b,t,s] over the positions s of class c
+        d loglik[b] / d log_stay[b,s]    = the expected number of stays in s, likewise next, skip
+
+    each times grad_loglik[b].  For a pair with a path every frame's log_probs gradient sums to 1
+    and the three transition gradients together to T_b - 1; a pair with no path (loglik = -inf)
+    contributes exact zeros, not NaN, and so do frames and positions past either length.
+
+        loglik = ForcedLogLik.apply(log_probs, state_ids, input_lengths, state_lengths,
+                                    log_stay, log_next, log_skip)
+    """
+
+    @staticmethod
+    def forward(ctx, log_probs, state_ids, input_lengths, state_lengths, log_stay=None, log_next=None, log_skip=None):
+        from . import ops
+        det = [None if t is None else t.detach() for t in (log_probs, log_stay, log_next, log_skip)]
+        loglik, alpha, beta, _, _, _ = ops.forced(det[0], state_ids, input_lengths, state_lengths, det[1], det[2],
+                                                  det[3], alpha=True, beta=True)
+        ctx.save_for_backward(alpha, beta, loglik, det[0], state_ids, torch.as_tensor(input_lengths),
+                              torch.as_tensor(state_lengths), det[1], det[2], det[3])
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (log_probs, log_stay, log_next, log_skip))
+        return loglik
+
+    @staticmethod
+    def backward(ctx, grad_loglik):
+        from . import ops
+        alpha, beta, loglik, lp, ids, il, sl, ws, wn, wk = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = (need[0], ws is not None and need[4], wn is not None and need[5], wk is not None and need[6])
+        if not any(want):
+            return (None,) * 7
+        _, g_lp, g_s, g_n, g_k = ops.forced_grad(alpha, beta, loglik, lp, ids, il, sl, ws, wn, wk, want_gamma=False,
+                                                 want_grad=want[0], want_stay=want[1], want_next=want[2],
+                                                 want_skip=want[3])
+        g = grad_loglik.to(torch.float32)
+        out = []
+        for w, t, dt in zip(want, (g_lp, g_s, g_n, g_k), ctx.dtypes):
+            out.append((t * g.reshape((-1,) + (1,) * (t.dim() - 1))).to(dt) if w else None)
+        return out[0], None, None, None, out[1], out[2], out[3]
+
+
 class HsmmLogLik(torch.autograd.Function):
     """loglik (B) = log of the sum over segmentations of the explicit-duration model
     (ops.hsmm_forward_backward, csrc/hsmm_fb.hip), differentiable in lp (B,T,S), dur_lp (S,Dmax),

@@ -27,6 +27,11 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.duration_constrained_viterbi(emission_log_probs, log_transitions, min_duration,
                                                 max_duration, penalty_weight, per_sequence, want_trellis)
       -> (states, final_score, log_delta, durations)
+  torch.ops.hmm355.forced(log_probs, state_ids, input_lengths, state_lengths, log_stay, log_next, log_skip,
+                          alpha, beta, viterbi) -> (loglik, alpha, beta, path, score, durations)
+  torch.ops.hmm355.forced_grad(alpha, beta, loglik, log_probs, state_ids, input_lengths, state_lengths,
+                               log_stay, log_next, log_skip, want_gamma, want_grad, want_stay, want_next,
+                               want_skip) -> (gamma, grad_log_probs, grad_stay, grad_next, grad_skip)
 """
 from typing import Optional, Tuple
 
@@ -922,6 +927,176 @@ def _(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes, 
     B, T, S = alpha.shape
     return (alpha.new_empty((T, B, num_classes), dtype=torch.float32),
             alpha.new_empty((B, T, S) if want_gamma else _EMPTY, dtype=torch.float32))
+
+
+# ------------------------------------------------------------------ transcript forced alignment
+FORCED_ALPHA = nat.FORCED_ALPHA
+FORCED_BETA = nat.FORCED_BETA
+FORCED_VITERBI = nat.FORCED_VITERBI
+FORCED_MAX_POSITIONS = nat.FORCED_MAX_POSITIONS
+
+
+def _forced_args(shape, dev, state_ids, input_lengths, state_lengths, log_stay=None, log_next=None, log_skip=None):
+    """Checks the arguments of a forced-alignment call over log_probs of `shape` = (B,T,C) on the
+    host (ValueError) and returns (int32 state_ids (B,Smax) or None, int32 input and state lengths,
+    the three fp32 weight tensors (B,Smax) or None, all on `dev`, Smax): the layout the C ABI
+    takes.  Without state_ids the chain is the identity over the columns of log_probs (Smax = C,
+    or the width of a weight tensor if one is given).  The lengths (B values each) are read on the
+    host: the call's one synchronisation.  Ids are not checked: one outside [0, C) counts as an
+    emission of -inf."""
+    B, T, C = shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError(f"log_probs needs at least one sequence, frame and class; got {tuple(shape)}")
+    weights = (("log_stay", log_stay), ("log_next", log_next), ("log_skip", log_skip))
+    if state_ids is not None:
+        if state_ids.dim() != 2 or state_ids.shape[0] != B:
+            raise ValueError(f"state_ids must be (B, Smax) with B = {B}; got {tuple(state_ids.shape)}")
+        if state_ids.dtype.is_floating_point or state_ids.dtype == torch.bool:
+            raise ValueError(f"state_ids must hold integer class ids; got {state_ids.dtype}")
+        Smax = state_ids.shape[1]
+    else:
+        given = [w.shape[1] for _, w in weights if w is not None and w.dim() == 2]
+        Smax = given[0] if given else C
+        if Smax > C:
+            raise ValueError(f"without state_ids the chain is the columns of log_probs: {Smax} positions need "
+                             f"C >= {Smax}; got C = {C}")
+    if Smax < 1 or Smax > FORCED_MAX_POSITIONS:
+        raise ValueError(f"chains of 1 to {FORCED_MAX_POSITIONS} positions are supported; got {Smax}")
+    lens = []
+    for name, t, hi in (("input_lengths", input_lengths, T), ("state_lengths", state_lengths, Smax)):
+        t = torch.as_tensor(t)
+        if t.numel() != B:
+            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
+        host = t.detach().reshape(B).to("cpu", torch.int64)
+        if int(host.min()) < 1 or int(host.max()) > hi:
+            raise ValueError(f"{name} must lie in [1, {hi}]; got {host.tolist()}")
+        lens.append(host.to(torch.int32).to(dev))
+    ws = []
+    for name, w in weights:
+        if w is not None:
+            if tuple(w.shape) != (B, Smax):
+                raise ValueError(f"{name} must be (B, Smax) = ({B}, {Smax}); got {tuple(w.shape)}")
+            w = _f32c(w.detach().to(dev))
+        ws.append(w)
+    ids = None if state_ids is None else state_ids.detach().to(device=dev, dtype=torch.int32).contiguous()
+    return ids, lens[0], lens[1], ws[0], ws[1], ws[2], Smax
+
+
+@torch.library.custom_op("hmm355::forced", mutates_args=())
+def forced(log_probs: Tensor, state_ids: Optional[Tensor], input_lengths: Tensor, state_lengths: Tensor,
+           log_stay: Optional[Tensor] = None, log_next: Optional[Tensor] = None, log_skip: Optional[Tensor] = None,
+           alpha: bool = False, beta: bool = False,
+           viterbi: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The forced-alignment lattices of B utterances in one launch (hmm355_forced_f32,
+    csrc/forced.hip; the recursion is spelled out in include/hmm355.h).  log_probs (B,T,C);
+    state_ids (B,Smax) integer classes of the chain positions, or None for the identity chain
+    (monotonic alignment search over log_probs (B,T,S)); input_lengths / state_lengths (B) on any
+    device; log_stay / log_next / log_skip (B,Smax) per-position weights of s->s, s->s+1, s->s+2 or
+    None (0, 0, -inf: no skips).  Returns (loglik (B); alpha (B,T,Smax); beta (B,T,Smax), its own
+    frame's emission left out; path (B,T) int32 position of each frame on the best path, -1 past
+    input_lengths[b] and for a pair with no path; score (B) of that path; durations (B,Smax) int32
+    frames per position).  alpha / beta / viterbi select what is computed beyond loglik; the others
+    come back as empty tensors.  Lengths outside [1, T] / [1, Smax] raise ValueError."""
+    nat.require_gpu(log_probs, state_ids, log_stay, log_next, log_skip)
+    if log_probs.dim() != 3:
+        raise ValueError(f"log_probs must be (B, T, C); got {tuple(log_probs.shape)}")
+    dev = log_probs.device
+    ids, il, sl, ws, wn, wk, S = _forced_args(log_probs.shape, dev, state_ids, input_lengths, state_lengths,
+                                              log_stay, log_next, log_skip)
+    lp = _f32c(log_probs.detach())
+    B, T, C = lp.shape
+    A = torch.empty((B, T, S) if alpha else _EMPTY, device=dev)
+    Bt = torch.empty((B, T, S) if beta else _EMPTY, device=dev)
+    loglik = torch.empty(B, device=dev)
+    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    score = torch.empty(B if viterbi else 0, device=dev)
+    dur = torch.empty((B, S) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    flags = (FORCED_ALPHA if alpha else 0) | (FORCED_BETA if beta else 0) | (FORCED_VITERBI if viterbi else 0)
+    L = nat.lib()
+    wsp = _workspace(L.hmm355_forced_workspace_bytes(B, T, S, flags), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_forced_f32(
+            nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(ws), nat.ptr(wn), nat.ptr(wk), B, T, C, S,
+            flags, nat.ptr(A) if alpha else None, nat.ptr(Bt) if beta else None, nat.ptr(loglik),
+            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
+            nat.ptr(dur) if viterbi else None, nat.ptr(wsp), wsp.numel(), nat.stream_of(dev)))
+    return loglik, A, Bt, path, score, dur
+
+
+def _forced_width(log_probs, state_ids, log_stay, log_next, log_skip):
+    if state_ids is not None:
+        return state_ids.shape[1]
+    given = [w.shape[1] for w in (log_stay, log_next, log_skip) if w is not None]
+    return given[0] if given else log_probs.shape[2]
+
+
+@forced.register_fake
+def _(log_probs, state_ids, input_lengths, state_lengths, log_stay=None, log_next=None, log_skip=None, alpha=False,
+      beta=False, viterbi=False):
+    B, T, _ = log_probs.shape
+    S = _forced_width(log_probs, state_ids, log_stay, log_next, log_skip)
+    f32 = torch.float32
+    return (log_probs.new_empty(B, dtype=f32),
+            log_probs.new_empty((B, T, S) if alpha else _EMPTY, dtype=f32),
+            log_probs.new_empty((B, T, S) if beta else _EMPTY, dtype=f32),
+            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
+            log_probs.new_empty(B if viterbi else 0, dtype=f32),
+            log_probs.new_empty((B, S) if viterbi else _EMPTY, dtype=torch.int32))
+
+
+@torch.library.custom_op("hmm355::forced_grad", mutates_args=())
+def forced_grad(alpha: Tensor, beta: Tensor, loglik: Tensor, log_probs: Tensor, state_ids: Optional[Tensor],
+                input_lengths: Tensor, state_lengths: Tensor, log_stay: Optional[Tensor] = None,
+                log_next: Optional[Tensor] = None, log_skip: Optional[Tensor] = None, want_gamma: bool = False,
+                want_grad: bool = True, want_stay: bool = False, want_next: bool = False,
+                want_skip: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(gamma (B,T,Smax), grad_log_probs (B,T,C), grad_stay, grad_next, grad_skip (B,Smax)) from the
+    alpha, beta and loglik of one ops.forced call on the same inputs (hmm355_forced_grad_f32):
+    gamma = exp(alpha + beta - loglik), grad_log_probs[b,t,c] = the sum of gamma over the positions
+    of class c, and the expected number of times each stay / next / skip transition is taken.
+    Outputs not asked for come back as empty tensors (at least one must be asked for).  Zero past
+    either length and for a pair with no path; the same bits on every call.  Of log_probs only
+    the shape is used (alpha already holds its emissions)."""
+    nat.require_gpu(alpha, beta, loglik, log_probs, state_ids, log_stay, log_next, log_skip)
+    if alpha.dim() != 3 or alpha.shape != beta.shape:
+        raise ValueError(f"alpha and beta must both be (B, T, Smax); got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+    if log_probs.dim() != 3 or log_probs.shape[:2] != alpha.shape[:2]:
+        raise ValueError(f"log_probs must be (B, T, C) over alpha's B, T; got {tuple(log_probs.shape)}")
+    if not (want_gamma or want_grad or want_stay or want_next or want_skip):
+        raise ValueError("forced_grad: no output asked for")
+    B, T, S = alpha.shape
+    C = log_probs.shape[2]
+    if loglik.numel() != B:
+        raise ValueError(f"loglik must hold one value per sequence ({B}); got {tuple(loglik.shape)}")
+    dev = alpha.device
+    ids, il, sl, ws, wn, wk, Sk = _forced_args((B, T, C), dev, state_ids, input_lengths, state_lengths,
+                                               log_stay, log_next, log_skip)
+    if Sk != S:
+        raise ValueError(f"alpha has {S} positions; the chain arguments describe {Sk}")
+    alpha, beta, loglik = _f32c(alpha), _f32c(beta), _f32c(loglik)
+    out = [torch.empty(shape if want else _EMPTY, device=dev) for want, shape in (
+        (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S)))]
+    wants = (want_gamma, want_grad, want_stay, want_next, want_skip)
+    L = nat.lib()
+    trans = want_stay or want_next or want_skip     # their per-tile sums live in a workspace
+    wsp = _workspace(L.hmm355_forced_workspace_bytes(B, T, S, nat.FORCED_GRAD), dev) if trans else None
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_forced_grad_f32(
+            nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(ids), nat.ptr(il), nat.ptr(sl),
+            nat.ptr(ws), nat.ptr(wn), nat.ptr(wk), B, T, C, S,
+            *[nat.ptr(o) if w else None for o, w in zip(out, wants)], nat.ptr(wsp), wsp.numel() if trans else 0,
+            nat.stream_of(dev)))
+    return tuple(out)
+
+
+@forced_grad.register_fake
+def _(alpha, beta, loglik, log_probs, state_ids, input_lengths, state_lengths, log_stay=None, log_next=None,
+      log_skip=None, want_gamma=False, want_grad=True, want_stay=False, want_next=False, want_skip=False):
+    B, T, S = alpha.shape
+    C = log_probs.shape[2]
+    f32 = torch.float32
+    return tuple(alpha.new_empty(shape if want else _EMPTY, dtype=f32) for want, shape in (
+        (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S))))
 
 
 # ------------------------------------------------------------------ duration-constrained Viterbi
