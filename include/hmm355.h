@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -720,6 +720,96 @@ int hmm355_forced_grad_f32(const float* alpha, const float* beta, const float* l
                            float* grad_log_probs, float* grad_stay, float* grad_next,
                            float* grad_skip, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Explicit-duration forced alignment (csrc/durforced.hip): the transcript chain of the forced
+ * alignment above with the duration model of the HSMM in the place of stay / next weights.
+ * Sequence b has T_b = input_lengths[b] frames and L_b = state_lengths[b] positions; every position
+ * is visited once, in order (no skips), for d_l frames, 1 <= d_l <= Dmax, sum d_l = T_b exactly.
+ * One launch per call for the chains, one workgroup per sequence and job (forward sum, backward
+ * sum, max-plus forward with its walk).
+ *   log_probs (B,T,C) fp32 row-major, batch first; -inf entries are allowed, +inf and NaN are not
+ *   state_ids (B,Lmax) int32: the class (column of log_probs) of each position; only the first
+ *             state_lengths[b] of row b are read.  An id outside [0, C) is never used as an
+ *             index: its emission counts as -inf.  NULL: id_l = l (log_probs is already
+ *             (B,T,Lmax)); needs C >= Lmax, else HMM355_E_ARG
+ *   input_lengths, state_lengths  (B) int32 device arrays.  The caller guarantees
+ *             1 <= input_lengths[b] <= T and 1 <= state_lengths[b] <= Lmax (the Python layer
+ *             checks them on the host); the kernels clamp what they read to those ranges
+ *   dur_lp    (B,Lmax,Dmax) fp32: dur_lp[b,l,d-1] scores a segment of d frames for position l;
+ *             -inf forbids that duration (a minimum duration is a run of leading -inf)
+ * A segmentation scores sum_l dur_lp[b,l,d_l-1] + sum_t log_probs[b,t,id(position of t)].  With
+ * O(a..t,l) the sum of position l's emissions over frames a..t, tables (B,T,Lmax):
+ *   begin_0(0) = 0, begin_0(l>0) = -inf, begin_t(0) = -inf for t > 0
+ *   F_t(l)     = OP_{d <= min(Dmax,t+1)} begin_{t-d+1}(l) + O(t-d+1..t,l) + dur_lp[l,d-1]
+ *   begin_t+1(l+1) = F_t(l);   result = F_{T_b-1}(L_b-1)
+ *   Bend_{T_b-1}(L_b-1) = 0;  Bend_t(l) = Bbeg_t+1(l+1)
+ *   Bbeg_t(l)  = LSE_d dur_lp[l,d-1] + O(t..t+d-1,l) + Bend_{t+d-1}(l)
+ * OP is log-sum-exp for loglik and max for the best segmentation.  -inf candidates drop out of an
+ * LSE; no NaN is formed.  The recursions run on log_probs[b,t,id_l] - M_t, M_t the maximum over
+ * the chain's positions at frame t (0 where none is finite): every segmentation covers every frame
+ * once, so all scores move by sum_t M_t, which loglik and score get back in fp64.  The stored
+ * tables are those of the shifted scores; frames >= T_b and positions >= L_b are -inf.
+ * A pair is infeasible when T_b < L_b, T_b > L_b * Dmax or the -inf entries leave no
+ * segmentation: loglik / score -inf, path -1 everywhere, durations 0, gamma and gradients 0.
+ * T, B, C >= 1 (else HMM355_E_ARG); 1 <= Lmax <= HMM355_DURFORCED_MAX_POSITIONS, 1 <= Dmax <=
+ * HMM355_DURFORCED_MAX_DURATION and Lmax * Dmax <= HMM355_DURFORCED_MAX_CELLS (else
+ * HMM355_E_STATES: a sequence's open segments and its dur_lp live in one workgroup's LDS); B * T
+ * <= 2^31 and sizes that do not overflow (else HMM355_E_SHAPE); the size query returns 0 for any
+ * of them.  Every check comes before any launch.
+ *
+ * hmm355_durforced_f32
+ *   loglik (B): the log of the sum over segmentations; always produced.
+ *   flags  HMM355_DURFORCED_TABLES: run the backward sum too and store begin, F, Bend, Bbeg
+ *            (B,T,Lmax), frame_shift (B,T) = M_t (0 past T_b) and loglik_shifted (B) = loglik
+ *            without sum_t M_t: what hmm355_durforced_grad_f32 takes.  Without it no table is
+ *            written and those six pointers may be NULL.
+ *          HMM355_DURFORCED_VITERBI: the best segmentation.  Candidates are taken in ascending d
+ *            with strict >, so the smaller d wins a tie; the walk starts at position L_b - 1,
+ *            frame T_b - 1.  durations (B,Lmax) int32: d_l, 0 for l >= L_b; path (B,T) int32: the
+ *            position of every frame, -1 for frames >= T_b; score (B).
+ *   workspace >= hmm355_durforced_workspace_bytes(B, T, Lmax, Dmax, flags), 16-byte aligned (every
+ *          job's M_t; with HMM355_DURFORCED_VITERBI one byte per cell, the chosen d - 1).
+ * hmm355_durforced_grad_f32: from the tables of one hmm355_durforced_f32 call and the same
+ *   log_probs, ids, lengths and dur_lp, any of (at least one)
+ *   gamma (B,T,Lmax): the posterior of position l at frame t, the running sum over t of
+ *     P(l begins at t) - P(l ended at t - 1) = exp(begin + Bbeg - loglik_shifted) - exp(F + Bend -
+ *     loglik_shifted), exponents and sum in fp64;
+ *   grad_log_probs (B,T,C) = d loglik / d log_probs: the sum of gamma[b,t,l] over id_l = c;
+ *   grad_dur_lp (B,Lmax,Dmax) = d loglik / d dur_lp: grad_dur_lp[b,l,d-1] = sum_t exp(begin_{t-d+1}(l)
+ *     + O(t-d+1..t,l) + dur_lp[b,l,d-1] + Bend_t(l) - loglik_shifted), the expected number of
+ *     "position l lasts d frames"; O comes from fp64 prefix sums of the shifted emissions and a
+ *     running count of -inf frames.
+ *   For a feasible pair every used frame's gamma and every used position's grad_dur_lp row sum
+ *   to 1.  Three launches (gamma and prefix sums; counts per time chunk; the chunks added in
+ *   chunk order and the classes' gammas in position order); no atomics: two calls on the same
+ *   inputs return the same bits.
+ *   workspace: needed for grad_dur_lp, and for grad_log_probs without gamma (else it may be NULL):
+ *     >= hmm355_durforced_workspace_bytes(B, T, Lmax, Dmax, HMM355_DURFORCED_GRAD), 16-byte
+ *     aligned; HMM355_DURFORCED_GRAD is a flag of the size query alone (together with the others
+ *     it returns the larger need), and hmm355_durforced_f32 rejects it.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_DURFORCED_TABLES 0x1u
+#define HMM355_DURFORCED_VITERBI 0x2u
+#define HMM355_DURFORCED_GRAD 0x4u
+#define HMM355_DURFORCED_MAX_POSITIONS 1024
+#define HMM355_DURFORCED_MAX_DURATION 128
+#define HMM355_DURFORCED_MAX_CELLS 16384
+size_t hmm355_durforced_workspace_bytes(int B, int T, int Lmax, int Dmax, unsigned flags);
+int hmm355_durforced_f32(const float* log_probs, const int* state_ids, const int* input_lengths,
+                         const int* state_lengths, const float* dur_lp, int B, int T, int C,
+                         int Lmax, int Dmax, unsigned flags, float* begin, float* F, float* Bend,
+                         float* Bbeg, float* frame_shift, float* loglik_shifted, float* loglik,
+                         int* path, float* score, int* durations, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int hmm355_durforced_grad_f32(const float* begin, const float* F, const float* Bend,
+                              const float* Bbeg, const float* frame_shift,
+                              const float* loglik_shifted, const float* log_probs,
+                              const int* state_ids, const int* input_lengths,
+                              const int* state_lengths, const float* dur_lp, int B, int T, int C,
+                              int Lmax, int Dmax, float* gamma, float* grad_log_probs,
+                              float* grad_dur_lp, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,13 +25,16 @@ __all__ += ["HMMLayer", "GaussianHMMLayer", "MixtureGaussianHMMLayer", "HSMMLaye
             "StreamingHMMProcessor", "StreamingResult", "AdaptiveLatencyController"]
 
 from . import alignment
-from .alignment import (ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner, ForcedAligner,
+from .alignment import (ConstrainedDTWAligner, CTCAligner, CTCSegmentationAligner, DTWAligner,
+                        DurationForcedAligner, ForcedAligner, duration_forced_align, duration_forced_loglik,
+                        duration_forced_posteriors,
                         forced_align, forced_alignment_loglik, forced_alignment_posteriors,
                         monotonic_alignment_search)
 
 __all__ += ["alignment", "DTWAligner", "ConstrainedDTWAligner", "CTCAligner", "CTCSegmentationAligner",
             "ForcedAligner", "forced_align", "forced_alignment_loglik", "forced_alignment_posteriors",
-            "monotonic_alignment_search"]
+            "monotonic_alignment_search", "DurationForcedAligner", "duration_forced_align",
+            "duration_forced_loglik", "duration_forced_posteriors"]
 
 from .hsmm import DurationConstrainedHMM
 from .utils import compute_state_durations, create_duration_constrained_matrix

@@ -41,6 +41,11 @@ HSMM_FB_MAX_BATCH = 65535  # HMM355_HSMM_FB_MAX_BATCH: sequences per native call
 FORCED_ALPHA, FORCED_BETA, FORCED_VITERBI = 0x1, 0x2, 0x4  # HMM355_FORCED_* flags
 FORCED_GRAD = 0x8  # HMM355_FORCED_GRAD: the size query's flag for hmm355_forced_grad_f32's workspace
 FORCED_MAX_POSITIONS = 4096  # HMM355_FORCED_MAX_POSITIONS
+DURFORCED_TABLES, DURFORCED_VITERBI = 0x1, 0x2  # HMM355_DURFORCED_* flags
+DURFORCED_GRAD = 0x4  # HMM355_DURFORCED_GRAD: the size query's flag for hmm355_durforced_grad_f32's workspace
+DURFORCED_MAX_POSITIONS = 1024  # HMM355_DURFORCED_MAX_POSITIONS
+DURFORCED_MAX_DURATION = 128  # HMM355_DURFORCED_MAX_DURATION
+DURFORCED_MAX_CELLS = 16384  # HMM355_DURFORCED_MAX_CELLS: positions times max_duration
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -66,6 +71,7 @@ EXPORTS = (
     "hmm355_ctc_workspace_bytes", "hmm355_ctc_f32", "hmm355_ctc_grad_f32",
     "hmm355_dchmm_workspace_bytes", "hmm355_dchmm_viterbi_f32",
     "hmm355_forced_workspace_bytes", "hmm355_forced_f32", "hmm355_forced_grad_f32",
+    "hmm355_durforced_workspace_bytes", "hmm355_durforced_f32", "hmm355_durforced_grad_f32",
 )
 
 _lib = None
@@ -171,6 +177,11 @@ def lib():
     L.hmm355_forced_f32.restype = I
     L.hmm355_forced_grad_f32.argtypes = [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, S, P]
     L.hmm355_forced_grad_f32.restype = I
+    L.hmm355_durforced_workspace_bytes.argtypes, L.hmm355_durforced_workspace_bytes.restype = [I, I, I, I, U], S
+    L.hmm355_durforced_f32.argtypes = [P, P, P, P, P, I, I, I, I, I, U, P, P, P, P, P, P, P, P, P, P, P, S, P]
+    L.hmm355_durforced_f32.restype = I
+    L.hmm355_durforced_grad_f32.argtypes = [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, S, P]
+    L.hmm355_durforced_grad_f32.restype = I
     _lib = L
     return L
 

@@ -21,6 +21,13 @@ in both lengths) in one launch of csrc/forced.hip -- the best path with per-posi
 (forced_align, monotonic_alignment_search), the differentiable sum over all paths
 (forced_alignment_loglik, autograd.ForcedLogLik), the posteriors, and the ForcedAligner module.
 
+Explicit-duration forced alignment (durforced.py) is the same chain with a duration distribution
+per position in the place of stay / next weights (dur_lp (B,Lmax,Dmax), -inf for a forbidden
+duration), one launch of csrc/durforced.hip: the best segmentation (duration_forced_align), the
+differentiable sum over all segmentations (duration_forced_loglik, autograd.DurForcedLogLik), the
+position and duration posteriors, and the DurationForcedAligner module -- the alignment side of the
+reference's phoneme-duration workflows (HSMMLayer, DurationModel, phoneme_audio_alignment).
+
 The kernels take tensors on a ROCm GPU only.  Of the reference package's four listed techniques
 (DTW, CTC, attention, monotonic) it implements the first two; this package adds the monotonic one.
 """
@@ -29,6 +36,8 @@ from .ctc import (CTCAligner, CTCSegmentationAligner, collapse_repeated_tokens, 
                   expand_targets_with_blank, remove_ctc_blanks)
 from .dtw import (ConstrainedDTWAligner, DTWAligner, compute_distance_matrix, compute_dtw_path, dtw_alignment,
                   dtw_distance, extract_phoneme_durations, phoneme_audio_alignment)
+from .durforced import (DurationForcedAligner, duration_forced_align, duration_forced_loglik,
+                        duration_forced_posteriors)
 from .forced import (ForcedAligner, forced_align, forced_alignment_loglik, forced_alignment_posteriors,
                      monotonic_alignment_search)
 
@@ -38,4 +47,5 @@ __all__ = ["DTWAligner", "ConstrainedDTWAligner", "compute_distance_matrix", "co
            "ctc_alignment_path", "ctc_forced_align", "expand_targets_with_blank", "remove_ctc_blanks",
            "collapse_repeated_tokens", "ctc_decode_sequence",
            "ForcedAligner", "forced_align", "forced_alignment_loglik", "forced_alignment_posteriors",
-           "monotonic_alignment_search"]
+           "monotonic_alignment_search",
+           "DurationForcedAligner", "duration_forced_align", "duration_forced_loglik", "duration_forced_posteriors"]

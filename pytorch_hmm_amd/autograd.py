@@ -637,6 +637,47 @@ class ForcedLogLik(torch.autograd.Function):
         return out[0], None, None, None, out[1], out[2], out[3]
 
 
+class DurForcedLogLik(torch.autograd.Function):
+    """loglik (B) = the log of the sum over every segmentation of an utterance along its own
+    transcript chain with explicit per-position duration scores (ops.durforced,
+    csrc/durforced.hip), differentiable in log_probs (B,T,C) and dur_lp (B,Lmax,Dmax).  The
+    forward keeps the four tables; the backward is one ops.durforced_grad call that forms only
+    the gradients needs_input_grad asks for:
+
+        d loglik[b] / d log_probs[b,t,c] = sum of gamma[b,t,l] over the positions l of class c
+        d loglik[b] / d dur_lp[b,l,d-1]  = the expected number of "position l lasts d frames"
+
+    each times grad_loglik[b].  For a feasible pair every used frame's log_probs gradient and every
+    used position's dur_lp gradient sum to 1; an infeasible pair (loglik = -inf) contributes exact
+    zeros, not NaN, and so do frames and positions past either length.
+
+        loglik = DurForcedLogLik.apply(log_probs, state_ids, input_lengths, state_lengths, dur_lp)
+    """
+
+    @staticmethod
+    def forward(ctx, log_probs, state_ids, input_lengths, state_lengths, dur_lp):
+        from . import ops
+        lp, du = log_probs.detach(), dur_lp.detach()
+        loglik, begin, F, Bend, Bbeg, shift, lls, _, _, _ = ops.durforced(lp, state_ids, input_lengths, state_lengths,
+                                                                          du, tables=True)
+        ctx.save_for_backward(begin, F, Bend, Bbeg, shift, lls, lp, state_ids, torch.as_tensor(input_lengths),
+                              torch.as_tensor(state_lengths), du)
+        ctx.dtypes = (log_probs.dtype, dur_lp.dtype)
+        return loglik
+
+    @staticmethod
+    def backward(ctx, grad_loglik):
+        from . import ops
+        need = ctx.needs_input_grad
+        want = (need[0], need[4])
+        if not any(want):
+            return (None,) * 5
+        _, g_lp, g_du = ops.durforced_grad(*ctx.saved_tensors, want_gamma=False, want_grad=want[0], want_dur=want[1])
+        g = grad_loglik.to(torch.float32)
+        out = [(t * g.reshape(-1, 1, 1)).to(dt) if w else None for w, t, dt in zip(want, (g_lp, g_du), ctx.dtypes)]
+        return out[0], None, None, None, out[1]
+
+
 class HsmmLogLik(torch.autograd.Function):
     """loglik (B) = log of the sum over segmentations of the explicit-duration model
     (ops.hsmm_forward_backward, csrc/hsmm_fb.hip), differentiable in lp (B,T,S), dur_lp (S,Dmax),

@@ -32,6 +32,11 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.forced_grad(alpha, beta, loglik, log_probs, state_ids, input_lengths, state_lengths,
                                log_stay, log_next, log_skip, want_gamma, want_grad, want_stay, want_next,
                                want_skip) -> (gamma, grad_log_probs, grad_stay, grad_next, grad_skip)
+  torch.ops.hmm355.durforced(log_probs, state_ids, input_lengths, state_lengths, dur_lp, tables=, viterbi=)
+      -> (loglik, begin, F, Bend, Bbeg, frame_shift, loglik_shifted, path, score, durations)
+  torch.ops.hmm355.durforced_grad(begin, F, Bend, Bbeg, frame_shift, loglik_shifted, log_probs, state_ids,
+                                  input_lengths, state_lengths, dur_lp, want_gamma=, want_grad=, want_dur=)
+      -> (gamma, grad_log_probs, grad_dur_lp)
 """
 from typing import Optional, Tuple
 
@@ -1097,6 +1102,168 @@ def _(alpha, beta, loglik, log_probs, state_ids, input_lengths, state_lengths, l
     f32 = torch.float32
     return tuple(alpha.new_empty(shape if want else _EMPTY, dtype=f32) for want, shape in (
         (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S))))
+
+
+# ------------------------------------------------------------------ explicit-duration forced alignment
+DURFORCED_MAX_POSITIONS = nat.DURFORCED_MAX_POSITIONS
+DURFORCED_MAX_DURATION = nat.DURFORCED_MAX_DURATION
+DURFORCED_MAX_CELLS = nat.DURFORCED_MAX_CELLS
+_DURFORCED_TABLES = ("begin", "F", "Bend", "Bbeg")
+
+
+def durforced_supported(Lmax: int, Dmax: int) -> bool:
+    """The sizes durforced takes (csrc/durforced.hip: a sequence's open segments and its dur_lp
+    live in one workgroup's LDS)."""
+    return (1 <= Lmax <= DURFORCED_MAX_POSITIONS and 1 <= Dmax <= DURFORCED_MAX_DURATION and
+            Lmax * Dmax <= DURFORCED_MAX_CELLS)
+
+
+def _durforced_args(log_probs, dev, state_ids, input_lengths, state_lengths, dur_lp):
+    """Checks the arguments of an explicit-duration forced-alignment call on the host, before any
+    device call (ValueError; sizes beyond the kernel's limits raise the native library's error,
+    which names them), and returns (int32 state_ids (B,Lmax) or None, int32 input and state
+    lengths, fp32 dur_lp (B,Lmax,Dmax), all on `dev`, Lmax, Dmax): the layout the C ABI takes.
+    The lengths (B values each) are read on the host: the call's one synchronisation.  Ids are
+    not checked: one outside [0, C) counts as an emission of -inf."""
+    if log_probs.dim() != 3:
+        raise ValueError(f"log_probs must be (B, T, C); got {tuple(log_probs.shape)}")
+    if not log_probs.dtype.is_floating_point:
+        raise ValueError(f"log_probs must be a floating-point tensor; got {log_probs.dtype}")
+    B, T, C = log_probs.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError(f"log_probs needs at least one sequence, frame and class; got {tuple(log_probs.shape)}")
+    if dur_lp.dim() != 3 or dur_lp.shape[0] != B:
+        raise ValueError(f"dur_lp must be (B, Lmax, Dmax) with B = {B}; got {tuple(dur_lp.shape)}")
+    if not dur_lp.dtype.is_floating_point:
+        raise ValueError(f"dur_lp must be a floating-point tensor; got {dur_lp.dtype}")
+    Lmax, Dmax = dur_lp.shape[1], dur_lp.shape[2]
+    if state_ids is not None:
+        if state_ids.dim() != 2 or tuple(state_ids.shape) != (B, Lmax):
+            raise ValueError(f"state_ids must be (B, Lmax) = ({B}, {Lmax}); got {tuple(state_ids.shape)}")
+        if state_ids.dtype.is_floating_point or state_ids.dtype == torch.bool:
+            raise ValueError(f"state_ids must hold integer class ids; got {state_ids.dtype}")
+    elif Lmax > C:
+        raise ValueError(f"without state_ids the chain is the columns of log_probs: {Lmax} positions need "
+                         f"C >= {Lmax}; got C = {C}")
+    if not durforced_supported(Lmax, Dmax):
+        # the native call names what is wrong with the shape (nothing is launched)
+        nat.check(nat.lib().hmm355_durforced_f32(None, None, None, None, None, B, T, C, Lmax, Dmax, 0, None, None,
+                                                 None, None, None, None, None, None, None, None, None, 0, None))
+        raise ValueError(f"dur_lp of {Lmax} positions x {Dmax} durations is outside the supported sizes")
+    lens = []
+    for name, t, hi in (("input_lengths", input_lengths, T), ("state_lengths", state_lengths, Lmax)):
+        t = torch.as_tensor(t)
+        if t.numel() != B:
+            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"{name} must hold integers; got {t.dtype}")
+        host = t.detach().reshape(B).to("cpu", torch.int64)
+        if int(host.min()) < 1 or int(host.max()) > hi:
+            raise ValueError(f"{name} must lie in [1, {hi}]; got {host.tolist()}")
+        lens.append(host.to(torch.int32).to(dev))
+    ids = None if state_ids is None else state_ids.detach().to(device=dev, dtype=torch.int32).contiguous()
+    return ids, lens[0], lens[1], _f32c(dur_lp.detach().to(dev)), Lmax, Dmax
+
+
+@torch.library.custom_op("hmm355::durforced", mutates_args=())
+def durforced(log_probs: Tensor, state_ids: Optional[Tensor], input_lengths: Tensor, state_lengths: Tensor,
+              dur_lp: Tensor, *, tables: bool = False, viterbi: bool = False
+              ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Explicit-duration forced alignment of B utterances in one launch (hmm355_durforced_f32,
+    csrc/durforced.hip; the recursions are spelled out in include/hmm355.h).  log_probs (B,T,C);
+    state_ids (B,Lmax) integer classes of the chain positions, or None for the identity chain over
+    log_probs (B,T,Lmax); input_lengths / state_lengths (B) on any device; dur_lp (B,Lmax,Dmax),
+    dur_lp[b,l,d-1] the score of position l lasting d frames (-inf forbids it).  Returns (loglik
+    (B); begin, F, Bend, Bbeg (B,T,Lmax), frame_shift (B,T) and loglik_shifted (B): the tables
+    ops.durforced_grad takes; path (B,T) int32 position of each frame on the best segmentation, -1
+    past input_lengths[b] and for an infeasible pair; score (B); durations (B,Lmax) int32).
+    tables / viterbi select what is computed beyond loglik; the others come back as empty
+    tensors, and without tables no table is written.  Lengths outside [1, T] / [1, Lmax] raise
+    ValueError."""
+    nat.require_gpu(log_probs, state_ids, dur_lp)
+    dev = log_probs.device
+    ids, il, sl, du, Lm, Dm = _durforced_args(log_probs, dev, state_ids, input_lengths, state_lengths, dur_lp)
+    lp = _f32c(log_probs.detach())
+    B, T, C = lp.shape
+    tabs = [torch.empty((B, T, Lm) if tables else _EMPTY, device=dev) for _ in _DURFORCED_TABLES]
+    shift = torch.empty((B, T) if tables else _EMPTY, device=dev)
+    lls = torch.empty(B if tables else 0, device=dev)
+    loglik = torch.empty(B, device=dev)
+    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    score = torch.empty(B if viterbi else 0, device=dev)
+    dur = torch.empty((B, Lm) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    flags = (nat.DURFORCED_TABLES if tables else 0) | (nat.DURFORCED_VITERBI if viterbi else 0)
+    L = nat.lib()
+    wsp = _workspace(L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, flags), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_durforced_f32(
+            nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du), B, T, C, Lm, Dm, flags,
+            *[nat.ptr(t) if tables else None for t in (*tabs, shift, lls)], nat.ptr(loglik),
+            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
+            nat.ptr(dur) if viterbi else None, nat.ptr(wsp), wsp.numel(), nat.stream_of(dev)))
+    return (loglik, *tabs, shift, lls, path, score, dur)
+
+
+@durforced.register_fake
+def _(log_probs, state_ids, input_lengths, state_lengths, dur_lp, *, tables=False, viterbi=False):
+    B, T, _ = log_probs.shape
+    Lm = dur_lp.shape[1]
+    f32 = torch.float32
+    tab = lambda: log_probs.new_empty((B, T, Lm) if tables else _EMPTY, dtype=f32)
+    return (log_probs.new_empty(B, dtype=f32), tab(), tab(), tab(), tab(),
+            log_probs.new_empty((B, T) if tables else _EMPTY, dtype=f32),
+            log_probs.new_empty(B if tables else 0, dtype=f32),
+            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
+            log_probs.new_empty(B if viterbi else 0, dtype=f32),
+            log_probs.new_empty((B, Lm) if viterbi else _EMPTY, dtype=torch.int32))
+
+
+@torch.library.custom_op("hmm355::durforced_grad", mutates_args=())
+def durforced_grad(begin: Tensor, F: Tensor, Bend: Tensor, Bbeg: Tensor, frame_shift: Tensor, loglik_shifted: Tensor,
+                   log_probs: Tensor, state_ids: Optional[Tensor], input_lengths: Tensor, state_lengths: Tensor,
+                   dur_lp: Tensor, *, want_gamma: bool = False, want_grad: bool = True,
+                   want_dur: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """(gamma (B,T,Lmax), grad_log_probs (B,T,C), grad_dur_lp (B,Lmax,Dmax)) from the tables of one
+    ops.durforced(..., tables=True) call on the same inputs (hmm355_durforced_grad_f32): the
+    posterior of position l at frame t, its sum over the positions of each class (d loglik /
+    d log_probs) and the expected number of "position l lasts d frames" (d loglik / d dur_lp).
+    Outputs not asked for come back as empty tensors (at least one must be asked for).  Zero past
+    either length and for an infeasible pair; the same bits on every call."""
+    nat.require_gpu(begin, F, Bend, Bbeg, frame_shift, loglik_shifted, log_probs, state_ids, dur_lp)
+    if not (want_gamma or want_grad or want_dur):
+        raise ValueError("durforced_grad: no output asked for")
+    dev = log_probs.device
+    ids, il, sl, du, Lm, Dm = _durforced_args(log_probs, dev, state_ids, input_lengths, state_lengths, dur_lp)
+    B, T, C = log_probs.shape
+    for name, t in zip(_DURFORCED_TABLES, (begin, F, Bend, Bbeg)):
+        if tuple(t.shape) != (B, T, Lm):
+            raise ValueError(f"{name} must be (B, T, Lmax) = ({B}, {T}, {Lm}); got {tuple(t.shape)}")
+    if tuple(frame_shift.shape) != (B, T) or loglik_shifted.numel() != B:
+        raise ValueError(f"frame_shift must be ({B}, {T}) and loglik_shifted hold {B} values; got "
+                         f"{tuple(frame_shift.shape)} and {tuple(loglik_shifted.shape)}")
+    lp = _f32c(log_probs.detach())
+    tabs = [_f32c(t) for t in (begin, F, Bend, Bbeg, frame_shift, loglik_shifted)]
+    wants = (want_gamma, want_grad, want_dur)
+    out = [torch.empty(shape if want else _EMPTY, device=dev)
+           for want, shape in zip(wants, ((B, T, Lm), (B, T, C), (B, Lm, Dm)))]
+    L = nat.lib()
+    need_ws = want_dur or (want_grad and not want_gamma)
+    wsp = _workspace(L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, nat.DURFORCED_GRAD), dev) if need_ws else None
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_durforced_grad_f32(
+            *[nat.ptr(t) for t in tabs], nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du),
+            B, T, C, Lm, Dm, *[nat.ptr(o) if w else None for o, w in zip(out, wants)], nat.ptr(wsp),
+            wsp.numel() if need_ws else 0, nat.stream_of(dev)))
+    return tuple(out)
+
+
+@durforced_grad.register_fake
+def _(begin, F, Bend, Bbeg, frame_shift, loglik_shifted, log_probs, state_ids, input_lengths, state_lengths, dur_lp, *,
+      want_gamma=False, want_grad=True, want_dur=False):
+    B, T, C = log_probs.shape
+    Lm, Dm = dur_lp.shape[1], dur_lp.shape[2]
+    return tuple(log_probs.new_empty(shape if want else _EMPTY, dtype=torch.float32) for want, shape in (
+        (want_gamma, (B, T, Lm)), (want_grad, (B, T, C)), (want_dur, (B, Lm, Dm))))
 
 
 # ------------------------------------------------------------------ duration-constrained Viterbi
