@@ -243,6 +243,58 @@ int hmm355_forward_backward_wide_f32(const float* obs, int obs_mode, const float
                                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Padded batches with per-sequence lengths ("ragged", csrc/ragged.hip), 1 <= N <= 256.  Sequence b
+ * is the first lengths[b] frames of row b; the result is what hmm355_viterbi_f32 /
+ * hmm355_forward_backward_ex_f32 give for obs[b, :lengths[b]] alone.  Arguments and conventions
+ * as theirs, plus
+ *   lengths   (B) int32 device array.  The caller guarantees 1 <= lengths[b] <= T (the Python
+ *             layer checks it on the host); the kernels clamp what they read to that range.
+ * One workgroup per sequence and job (alpha chain, beta chain; Viterbi chain), each running
+ * exactly lengths[b] steps; no workgroup waits on another, no flags, no floating-point atomics:
+ * two calls on the same inputs return the same bits.  No plan.
+ * Padded frames t >= lengths[b]: the input there is never read (it may hold NaN or +-inf) and no
+ * output, workspace piece or gradient of any sequence depends on it.  posterior, forward and
+ * backward are 0 there, log_delta is -inf and states is -1.
+ *
+ * hmm355_viterbi_ragged_f32: delta_0 = init + lo_0, delta_t[j] = fl(max_i fl(delta_{t-1}[i] +
+ *   log_P[i][j]) + lo_t[j]), first index on ties, a column without a finite candidate index 0
+ *   (hmm.py:154-184); lo = log(x + 1e-8) correctly rounded for HMM355_OBS_PROB.  states and
+ *   log_delta of the valid frames are bit-identical to hmm355_viterbi_f32's on the slice.
+ *   states[b, lengths[b]-1] = the first argmax of delta[lengths[b]-1], final_score[b] (or NULL)
+ *   its value.  The backtrace runs in the chain's own workgroup.
+ *   workspace >= hmm355_viterbi_ragged_workspace_bytes(B,T,N,obs_mode): psi (B,T,NP) uint8,
+ *   NP = N padded to 64/128/256.
+ * hmm355_forward_backward_ragged_f32: the scaled recursion with a deferred normaliser (a step
+ *   stores its raw row, the next step divides by that row's sum):
+ *     U_0 = exp(log_p0) e_0;                      U_{t+1} = (A^T U_t) e_{t+1} / CA_t,  CA_t = sum_i U_t[i]
+ *     V_{len-1} = 1 or exp(log_beta_T - its max);  V_{t-1} = A (e_t V_t) / CB_t,   CB_t = sum_j e_t[j] V_t[j]
+ *   e_t as in hmm355_forward_backward_ex_f32 (x + 1e-8, or exp(x - M_t)); the log-scales LA / LB
+ *   are summed in fp64 after the chains.  loglik[b] = log sum_j alpha_{len-1}[j]; lik_ref[b] the
+ *   reference's saturating value at frame len - 1.  log_beta_T (B,N) or NULL applies at frame
+ *   lengths[b] - 1.  out_mask takes the three HMM355_FB_POSTERIOR / _FORWARD / _BACKWARD bits only.
+ *   workspace >= hmm355_fb_workspace_bytes(B,T,N), in the layout hmm355_fb_workspace_layout
+ *   reports: U | V (B,T,NP), LA | LB, .., M, CA | CB (B,T) with alpha_t = U_t exp(LA_t), beta_t =
+ *   V_t exp(LB_t), so hmm355_fb_adjoint_f32 and its callers read the same pieces at the same
+ *   offsets.  In frames t >= lengths[b]: U = V = 0, LA = LB = 0, CA = CB = 1; also CA = 1 at
+ *   lengths[b] - 1 and CB = 1 at frame 0 (no step divides by them).
+ * Status: HMM355_E_ARG for a null pointer (lengths included), a bad obs_mode, an unknown mask bit
+ * or a mask bit without its pointer; HMM355_E_STATES for N outside [1, 256]; HMM355_E_SHAPE for
+ * T < 1 or a size that overflows; HMM355_E_WORKSPACE for a short workspace; B == 0 is a no-op.
+ * Every check comes before any launch.  The size query returns 0 for a rejected shape or mode.
+ * ------------------------------------------------------------------------------ */
+size_t hmm355_viterbi_ragged_workspace_bytes(int B, int T, int N, int obs_mode);
+int hmm355_viterbi_ragged_f32(const float* obs, int obs_mode, const float* log_P, const float* init,
+                              const int* lengths, int B, int T, int N, int64_t* states,
+                              float* log_delta, float* final_score, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int hmm355_forward_backward_ragged_f32(const float* obs, int obs_mode, const float* log_P,
+                                       const float* log_p0, const float* log_beta_T /* (B,N) or NULL */,
+                                       const int* lengths, int B, int T, int N, unsigned out_mask,
+                                       float* posterior, float* forward, float* backward,
+                                       float* loglik, float* lik_ref, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Diagonal-covariance Gaussian-mixture emission scorer.  Replaces
  * MixtureGaussianHMMLayer.get_observation_log_probs for covariance_type='diag'
  * (mixture_gaussian.py:157-214, LSE of :141-155) and, with C == 1 and log_w == 0,

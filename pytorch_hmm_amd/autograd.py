@@ -61,10 +61,12 @@ def _require_narrow(N, what):
             "forward-backward runs without autograd support (call it under torch.no_grad() / on detached inputs)")
 
 
-def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_mask=None, plan=None):
+def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_mask=None, plan=None, lengths=None):
     """One hmm355_forward_backward_plan_f32 call; returns (posterior|None, loglik, lik_ref, U, V,
     LA, LB), or with `out_mask` ((posterior, forward, backward) per the mask, loglik, lik_ref, U,
-    V, LA, LB)."""
+    V, LA, LB).  With `lengths` (host int64 (B), checked by ops.ragged_lengths) the call is
+    hmm355_forward_backward_ragged_f32: the same workspace pieces, zero rows and unit normalisers
+    in the padded frames (hmm355.h)."""
     B, T, N = obs.shape
     NP = _pad(N)
     dev = obs.device
@@ -76,10 +78,17 @@ def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_
     loglik = torch.empty(B, device=dev)
     lik_ref = torch.empty(B, device=dev)
     with torch.cuda.device(dev):
-        nat.check(L.hmm355_forward_backward_plan_f32(
-            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(plan), nat.ptr(log_beta_T), B, T, N,
-            mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
-            nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+        if lengths is not None:
+            lens = lengths.to(torch.int32).to(dev)
+            nat.check(L.hmm355_forward_backward_ragged_f32(
+                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(log_beta_T), nat.ptr(lens), B, T, N,
+                mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
+                nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+        else:
+            nat.check(L.hmm355_forward_backward_plan_f32(
+                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(plan), nat.ptr(log_beta_T), B, T, N,
+                mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
+                nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
     rows = B * T
     # the workspace pieces, at the offsets the library reports (hmm355_fb_workspace_layout)
     o = fb_layout(B, T, N)
@@ -96,14 +105,41 @@ def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_
     return post, loglik, lik_ref, U, V, LA, LB, CA, CB
 
 
-def _staged_emissions(obs, obs_mode):
+def valid_frames(lengths, T, dev):
+    """(B,T) bool: frame t of sequence b is one of its lengths[b] frames (None without lengths)."""
+    if lengths is None:
+        return None
+    return torch.arange(T, device=dev)[None, :] < lengths.to(dev)[:, None]
+
+
+def _staged_emissions(obs, obs_mode, valid=None):
     """The emissions the chains multiply by: obs + 1e-8 (OBS_PROB, hmm.py:86) or exp(obs - M_t)
-    with M_t the row maximum (OBS_LOG; 0 for a row without a finite maximum, hmm355.h)."""
+    with M_t the row maximum (OBS_LOG; 0 for a row without a finite maximum, hmm355.h).  With
+    `valid` (B,T) the padded frames are exactly 0 (selected, not multiplied: a NaN pad stays out)."""
+    if valid is not None:
+        obs = torch.where(valid[..., None], obs, torch.zeros_like(obs))
     if obs_mode == nat.OBS_PROB:
-        return obs + 1e-8
-    m = obs.amax(-1, keepdim=True)
-    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    return torch.exp(obs - m)
+        e = obs + 1e-8
+    else:
+        m = obs.amax(-1, keepdim=True)
+        m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+        e = torch.exp(obs - m)
+    return e if valid is None else torch.where(valid[..., None], e, torch.zeros_like(e))
+
+
+def _terminal_adjoint(a_last, kind):
+    """g = dL/d log alpha of the last frame (B,N) for the 'ref' / 'exact' likelihood, and
+    log(g / alpha): the terminal backward vector of the adjoint pass (module docstring)."""
+    if kind == "ref":
+        f = torch.exp(a_last)                                 # the reference's forward[:, -1]
+        z = torch.log(f + 1e-8)
+        w = torch.softmax(z, dim=-1)
+        g = w * f / (f + 1e-8)                                # dL/d log alpha_{T-1}
+        log_mu = torch.log(w) - z                             # log(g / alpha_{T-1})
+    else:
+        g = torch.softmax(a_last, dim=-1)
+        log_mu = torch.zeros_like(a_last)
+    return g, log_mu
 
 
 class SequenceLogLik(torch.autograd.Function):
@@ -111,30 +147,27 @@ class SequenceLogLik(torch.autograd.Function):
     log_P and log_p0."""
 
     @staticmethod
-    def forward(ctx, obs, log_P, log_p0, obs_mode, kind, plan=None):
+    def forward(ctx, obs, log_P, log_p0, obs_mode, kind, plan=None, lengths=None):
+        """lengths: host int64 (B) from ops.ragged_lengths, or None.  With it sequence b is
+        obs[b, :lengths[b]] (the ragged entry point); the gradients are those of the per-sequence
+        computations, grad_obs exactly 0 in the padded frames."""
         _require_narrow(obs.shape[-1], "the gradient of the sequence log-likelihood")
         nat.require_gpu(obs, log_P, log_p0)
         obs_c, lP, l0 = (t.detach().to(torch.float32).contiguous() for t in (obs, log_P, log_p0))
-        _, loglik, lik_ref, *_ = _run_fb(obs_c, lP, l0, obs_mode, plan=plan)
+        _, loglik, lik_ref, *_ = _run_fb(obs_c, lP, l0, obs_mode, plan=plan, lengths=lengths)
         ctx.save_for_backward(obs_c, lP, l0)
-        ctx.obs_mode, ctx.kind, ctx.plan = obs_mode, kind, plan
+        ctx.obs_mode, ctx.kind, ctx.plan, ctx.lengths = obs_mode, kind, plan, lengths
         return lik_ref if kind == "ref" else loglik
 
     @staticmethod
     def backward(ctx, gout):
         obs, lP, l0 = ctx.saved_tensors
         B, T, N = obs.shape
+        if ctx.lengths is not None:
+            return SequenceLogLik._backward_ragged(ctx, gout)
         _, _, _, U, _, LA, _, _, _ = _run_fb(obs, lP, l0, ctx.obs_mode, plan=ctx.plan)
         a_last = torch.log(U[:, -1]) + LA[:, -1:]                 # log alpha_{T-1}  (B,N)
-        if ctx.kind == "ref":
-            f = torch.exp(a_last)                                 # the reference's forward[:, -1]
-            z = torch.log(f + 1e-8)
-            w = torch.softmax(z, dim=-1)
-            g = w * f / (f + 1e-8)                                # dL/d log alpha_{T-1}
-            log_mu = torch.log(w) - z                             # log(g / alpha_{T-1})
-        else:
-            g = torch.softmax(a_last, dim=-1)
-            log_mu = torch.zeros_like(a_last)
+        g, log_mu = _terminal_adjoint(a_last, ctx.kind)
         G = g.sum(-1) * gout                                      # (B,)
         post, _, _, U, V, _, _, CA, _ = _run_fb(obs, lP, l0, ctx.obs_mode, log_beta_T=log_mu.contiguous(),
                                                 posterior=True, plan=ctx.plan)
@@ -158,7 +191,43 @@ class SequenceLogLik(torch.autograd.Function):
             Y = e[:, 1:] * V[:, 1:]
             M = torch.einsum("bti,btj->ij", X, Y)
             grad_lP = torch.exp(lP) * M
-        return grad_obs, grad_lP, grad_l0, None, None, None
+        return grad_obs, grad_lP, grad_l0, None, None, None, None
+
+    @staticmethod
+    def _backward_ragged(ctx, gout):
+        """backward() with per-sequence lengths: log alpha is taken at frame len_b - 1, the
+        emissions and every factor of the padded frames are selected to exactly 0 (torch.where: a
+        NaN pad stays out), and the transition pairs (t, t + 1) stop at len_b - 1."""
+        obs, lP, l0 = ctx.saved_tensors
+        B, T, N = obs.shape
+        lengths = ctx.lengths
+        dev = obs.device
+        valid = valid_frames(lengths, T, dev)                    # (B,T)
+        last = (lengths.to(dev) - 1)
+        rows = torch.arange(B, device=dev)
+        _, _, _, U, _, LA, _, _, _ = _run_fb(obs, lP, l0, ctx.obs_mode, lengths=lengths)
+        a_last = torch.log(U[rows, last]) + LA[rows, last][:, None]   # log alpha_{len-1}  (B,N)
+        g, log_mu = _terminal_adjoint(a_last, ctx.kind)
+        G = g.sum(-1) * gout
+        post, _, _, U, V, _, _, CA, _ = _run_fb(obs, lP, l0, ctx.obs_mode, log_beta_T=log_mu.contiguous(),
+                                                posterior=True, lengths=lengths)
+        grad_lo = G[:, None, None] * post                         # post is 0 in the padded frames
+        e = _staged_emissions(obs, ctx.obs_mode, valid)
+        if ctx.obs_mode == nat.OBS_PROB:
+            grad_obs = torch.where(valid[..., None], grad_lo / (obs + 1e-8), torch.zeros_like(grad_lo))
+        else:
+            grad_obs = grad_lo
+        grad_l0 = (G[:, None] * post[:, 0]).sum(0)
+        grad_lP = None
+        if T > 1 and ctx.needs_input_grad[1]:
+            pair = valid[:, 1:, None]                             # frames t and t + 1 both valid
+            S = (U * V).sum(-1)
+            den = (CA[:, :-1] * S[:, 1:]).unsqueeze(-1)
+            X = torch.where(pair, U[:, :-1] / torch.where(pair, den, torch.ones_like(den)), torch.zeros_like(U[:, :-1]))
+            X = X * G[:, None, None]
+            Y = e[:, 1:] * V[:, 1:]
+            grad_lP = torch.exp(lP) * torch.einsum("bti,btj->ij", X, Y)
+        return grad_obs, grad_lP, grad_l0, None, None, None, None
 
 
 def _run_tv_fb(log_obs, A, sb, st, log_p0, log_beta_T=None, posterior=False, out_mask=None):
@@ -310,14 +379,18 @@ class ForwardBackwardFn(torch.autograd.Function):
     (two GEMMs over the frames, hipBLASLt through torch)."""
 
     @staticmethod
-    def forward(ctx, obs, log_P, log_p0, obs_mode, out_mask, plan=None):
+    def forward(ctx, obs, log_P, log_p0, obs_mode, out_mask, plan=None, lengths=None):
+        """lengths: host int64 (B) from ops.ragged_lengths, or None.  With it the rows come from
+        the ragged entry point: U = V = 0 and unit normalisers in the padded frames, so the W chain
+        of hmm355_fb_adjoint_f32 stays 0 down to frame len_b - 1, where it equals its source, and
+        the Z chain propagates zeros past it."""
         nat.require_gpu(obs, log_P, log_p0)
         obs_c, lP, l0 = (t.detach().to(torch.float32).contiguous() for t in (obs, log_P, log_p0))
         outs, _, _, U, V, _, _, CA, CB = _run_fb(obs_c, lP, l0, obs_mode, out_mask=out_mask | nat.FB_POSTERIOR,
-                                                 plan=plan)
+                                                 plan=plan, lengths=lengths)
         post, fwd, bwd = outs
         ctx.save_for_backward(obs_c, lP, l0, U, V, post, fwd, bwd, CA, CB)
-        ctx.obs_mode, ctx.out_mask = obs_mode, out_mask
+        ctx.obs_mode, ctx.out_mask, ctx.lengths = obs_mode, out_mask, lengths
         ctx.set_materialize_grads(False)   # outputs the loss does not use arrive as None
         res = tuple(o for bit, o in ((nat.FB_POSTERIOR, post), (nat.FB_FORWARD, fwd), (nat.FB_BACKWARD, bwd))
                     if out_mask & bit)
@@ -331,7 +404,12 @@ class ForwardBackwardFn(torch.autograd.Function):
                     if ctx.out_mask & bit]
         got = dict(zip(returned, grads))
         gp, gf, gb = got.get("p"), got.get("f"), got.get("b")
-        E = _staged_emissions(obs, ctx.obs_mode).contiguous()
+        valid = valid_frames(ctx.lengths, T, obs.device)
+        if valid is not None:
+            # sources are 0 in the padded frames whatever the incoming gradient holds there
+            gp, gf, gb = (None if g is None else torch.where(valid[..., None], g, torch.zeros_like(g))
+                          for g in (gp, gf, gb))
+        E = _staged_emissions(obs, ctx.obs_mode, valid).contiguous()
         srcW, Fw, srcZ, Fz = _adjoint_sources(U, V, E, post, fwd, bwd, gp, gf, gb, CA, CB)
         W = torch.empty(B, T, N, device=obs.device)
         P = torch.empty(B, T, N, device=obs.device)
@@ -342,6 +420,8 @@ class ForwardBackwardFn(torch.autograd.Function):
                                               nat.stream_of(obs.device)))
         grad_lo = U * W + V * P
         grad_obs = grad_lo / (obs + 1e-8) if ctx.obs_mode == nat.OBS_PROB else grad_lo
+        if valid is not None:
+            grad_obs = torch.where(valid[..., None], grad_obs, torch.zeros_like(grad_obs))
         grad_l0 = (U[:, 0] * W[:, 0]).sum(0)
         grad_lP = None
         if ctx.needs_input_grad[1]:
@@ -353,7 +433,7 @@ class ForwardBackwardFn(torch.autograd.Function):
                 Y2 = E[:, 1:] * V[:, 1:] * Fz[:, 1:, None]
                 M = torch.einsum("bti,btj->ij", X1, Y1) + torch.einsum("bti,btj->ij", Z[:, :-1], Y2)
             grad_lP = torch.exp(lP) * M
-        return grad_obs, grad_lP, grad_l0, None, None, None
+        return grad_obs, grad_lP, grad_l0, None, None, None, None
 
 
 class TvForwardBackwardFn(torch.autograd.Function):
@@ -432,10 +512,11 @@ def tv_forward_backward_with_grad(log_obs, log_A, log_p0, out_mask):
     return TvForwardBackwardFn.apply(log_obs, log_A, log_p0, out_mask)
 
 
-def forward_backward_with_grad(obs, log_P, log_p0, obs_mode, out_mask, plan=None):
-    """Differentiable forward-backward outputs (tuple per out_mask: posterior, forward, backward)."""
+def forward_backward_with_grad(obs, log_P, log_p0, obs_mode, out_mask, plan=None, lengths=None):
+    """Differentiable forward-backward outputs (tuple per out_mask: posterior, forward, backward).
+    lengths: host int64 (B) from ops.ragged_lengths, or None."""
     _require_narrow(obs.shape[-1], "the gradient of the forward-backward outputs")
-    return ForwardBackwardFn.apply(obs, log_P, log_p0, obs_mode, out_mask, plan)
+    return ForwardBackwardFn.apply(obs, log_P, log_p0, obs_mode, out_mask, plan, lengths)
 
 
 class GmmLogProb(torch.autograd.Function):
@@ -506,11 +587,18 @@ class ViterbiScore(torch.autograd.Function):
     routes it along the decoded path only — d/d lp[b,t,s_t] = g_b, d/d log_T[s_{t-1},s_t] += g_b."""
 
     @staticmethod
-    def forward(ctx, lp, log_T, init, plan=None):
+    def forward(ctx, lp, log_T, init, plan=None, lengths=None):
+        """lengths: per-sequence lengths (ops.viterbi_ragged) or None.  With them the score is
+        max_j delta[len_b - 1][j], states is -1 in the padded frames and the gradient follows the
+        decoded path over the valid frames only."""
         from . import ops
-        states, _, final = ops.viterbi(lp.detach(), log_T.detach(), init.detach(), ops.OBS_LOG, plan)
+        if lengths is None:
+            states, _, final = ops.viterbi(lp.detach(), log_T.detach(), init.detach(), ops.OBS_LOG, plan)
+        else:
+            states, _, final = ops.viterbi_ragged(lp.detach(), log_T.detach(), init.detach(), ops.OBS_LOG, lengths)
         ctx.save_for_backward(states)
         ctx.shapes = (lp.shape, log_T.shape)
+        ctx.ragged = lengths is not None
         ctx.mark_non_differentiable(states)
         return states, final
 
@@ -518,6 +606,17 @@ class ViterbiScore(torch.autograd.Function):
     def backward(ctx, g_states, g):
         (states,) = ctx.saved_tensors
         (B, T, S), _ = ctx.shapes
+        if ctx.ragged:
+            # a padded frame (state -1) routes a zero to state 0
+            on = states >= 0
+            gt = g.view(B, 1) * on
+            path = states.clamp(min=0)
+            grad_lp = torch.zeros(B, T, S, device=g.device).scatter_(2, path.unsqueeze(-1), gt.unsqueeze(-1))
+            grad_T = torch.zeros(S * S, device=g.device)
+            if T > 1:
+                grad_T.index_add_(0, (path[:, :-1] * S + path[:, 1:]).reshape(-1), gt[:, 1:].reshape(-1))
+            grad_init = torch.zeros(S, device=g.device).index_add_(0, path[:, 0], g)
+            return grad_lp, grad_T.view(S, S), grad_init, None, None
         grad_lp = torch.zeros(B, T, S, device=g.device)
         grad_lp.scatter_(2, states.unsqueeze(-1), g.view(B, 1, 1).expand(B, T, 1).contiguous())
         grad_T = torch.zeros(S * S, device=g.device)
@@ -525,7 +624,7 @@ class ViterbiScore(torch.autograd.Function):
             idx = (states[:, :-1] * S + states[:, 1:]).reshape(-1)
             grad_T.index_add_(0, idx, g.view(B, 1).expand(B, T - 1).reshape(-1))
         grad_init = torch.zeros(S, device=g.device).index_add_(0, states[:, 0], g)
-        return grad_lp, grad_T.view(S, S), grad_init, None
+        return grad_lp, grad_T.view(S, S), grad_init, None, None
 
 
 class SoftDTW(torch.autograd.Function):

@@ -79,15 +79,24 @@ class HMMPyTorch(HMM):
         return observations, False
 
     # -- reference API -------------------------------------------------------------
-    def forward_backward(self, observations: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def forward_backward(self, observations: torch.Tensor,
+                         lengths=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(posterior, forward, backward), each (B,T,K) — 2-D input is NOT squeezed, as in
         the reference (hmm.py:66-130).  forward/backward are exp(log alpha)/exp(log beta) and
-        underflow to 0 for long sequences exactly as the reference's do."""
+        underflow to 0 for long sequences exactly as the reference's do.
+
+        lengths (here and in the methods below; None = every sequence has T frames): one length
+        per sequence of a padded batch, a tensor, list or numpy array of B integers in [1, T].
+        Sequence b is observations[b, :lengths[b]]; the frames past it are never read and get
+        posterior = forward = backward = 0, log_delta = -inf and state -1."""
         obs, _ = self._as_batch(observations)
         B, T, K = obs.shape
         assert K == self.K, f"Observation dim {K} must match model states {self.K}"
         log_P, log_p0, plan = self._device_params(obs.device)
         mask = ops.FB_POSTERIOR | ops.FB_FORWARD | ops.FB_BACKWARD
+        lens = ops.active_lengths(lengths, B, T, K)
+        if lens is not None:
+            return self._fb_ragged(obs, log_P, log_p0, mask, lens)
         if needs_grad(obs, log_P, log_p0):
             # differentiable through all three outputs (autograd.ForwardBackwardFn)
             return forward_backward_with_grad(obs, log_P, log_p0, ops.OBS_PROB, mask, plan)
@@ -95,51 +104,66 @@ class HMMPyTorch(HMM):
                                                     mask, plan)
         return post, fwd, bwd
 
-    def posteriors(self, observations: torch.Tensor) -> torch.Tensor:
+    @staticmethod
+    def _fb_ragged(obs, log_P, log_p0, mask, lens):
+        """The outputs of `mask` for a padded batch with lengths `lens` (ops.active_lengths)."""
+        if needs_grad(obs, log_P, log_p0):
+            return forward_backward_with_grad(obs, log_P, log_p0, ops.OBS_PROB, mask, None, lens)
+        outs = ops.forward_backward_ragged(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB, lens, mask)
+        return tuple(o for bit, o in zip((ops.FB_POSTERIOR, ops.FB_FORWARD, ops.FB_BACKWARD), outs) if mask & bit)
+
+    def posteriors(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
         """Posterior only (what HMMLayer needs); skips the forward/backward outputs."""
         obs, _ = self._as_batch(observations)
         assert obs.shape[-1] == self.K, f"Observation dim {obs.shape[-1]} must match model states {self.K}"
         log_P, log_p0, plan = self._device_params(obs.device)
+        lens = ops.active_lengths(lengths, obs.shape[0], obs.shape[1], self.K)
+        if lens is not None:
+            return self._fb_ragged(obs, log_P, log_p0, ops.FB_POSTERIOR, lens)[0]
         if needs_grad(obs, log_P, log_p0):
             return forward_backward_with_grad(obs, log_P, log_p0, ops.OBS_PROB, ops.FB_POSTERIOR, plan)[0]
         return ops.forward_backward(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB,
                                     ops.FB_POSTERIOR, plan)[0]
 
-    def viterbi_decode(self, observations: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def viterbi_decode(self, observations: torch.Tensor, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(states (B,T) int64, log_delta (B,T,K)); 2-D input squeezed (hmm.py:132-184)."""
         obs, squeeze = self._as_batch(observations)
         B, T, K = obs.shape
         assert K == self.K, f"Observation dim {K} must match model states {self.K}"
         log_P, log_p0, plan = self._device_params(obs.device)
-        states, delta, _ = ops.viterbi(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB, plan)
+        lens = ops.active_lengths(lengths, B, T, K)
+        if lens is not None:
+            states, delta, _ = ops.viterbi_ragged(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB, lens)
+        else:
+            states, delta, _ = ops.viterbi(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB, plan)
         if squeeze:
             return states.squeeze(0), delta.squeeze(0)
         return states, delta
 
-    def compute_likelihood(self, observations: torch.Tensor) -> torch.Tensor:
-        """The reference's value logsumexp(log(forward[:, -1] + 1e-8)) (hmm.py:186-211),
-        including its saturation at log(K*1e-8) once exp(log alpha) underflows."""
+    def _likelihood(self, observations, lengths, kind):
+        """compute_likelihood ('ref') / log_likelihood ('exact'), taken at frame lengths[b] - 1."""
         obs, squeeze = self._as_batch(observations)
         B, T, K = obs.shape
         assert K == self.K, f"Observation dim {K} must match model states {self.K}"
         log_P, log_p0, plan = self._device_params(obs.device)
+        lens = ops.active_lengths(lengths, B, T, K)
         if needs_grad(obs, log_P, log_p0):
-            ll = SequenceLogLik.apply(obs, log_P, log_p0, ops.OBS_PROB, "ref")
+            ll = SequenceLogLik.apply(obs, log_P, log_p0, ops.OBS_PROB, kind, None, lens)
+        elif lens is not None:
+            ll = ops.forward_backward_ragged(obs, log_P, log_p0, ops.OBS_PROB, lens, 0)[4 if kind == "ref" else 3]
         else:
-            ll = ops.forward_backward(obs, log_P, log_p0, ops.OBS_PROB, 0, plan)[4]
+            ll = ops.forward_backward(obs, log_P, log_p0, ops.OBS_PROB, 0, plan)[4 if kind == "ref" else 3]
         return ll.squeeze(0) if squeeze else ll
 
-    def log_likelihood(self, observations: torch.Tensor) -> torch.Tensor:
+    def compute_likelihood(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
+        """The reference's value logsumexp(log(forward[:, -1] + 1e-8)) (hmm.py:186-211),
+        including its saturation at log(K*1e-8) once exp(log alpha) underflows."""
+        return self._likelihood(observations, lengths, "ref")
+
+    def log_likelihood(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
         """Extension: the well-defined sequence log-likelihood log sum_j alpha_{T-1}[j]
         (what compute_likelihood would return without exp() underflow)."""
-        obs, squeeze = self._as_batch(observations)
-        assert obs.shape[-1] == self.K, f"Observation dim {obs.shape[-1]} must match model states {self.K}"
-        log_P, log_p0, plan = self._device_params(obs.device)
-        if needs_grad(obs, log_P, log_p0):
-            ll = SequenceLogLik.apply(obs, log_P, log_p0, ops.OBS_PROB, "exact")
-        else:
-            ll = ops.forward_backward(obs, log_P, log_p0, ops.OBS_PROB, 0, plan)[3]
-        return ll.squeeze(0) if squeeze else ll
+        return self._likelihood(observations, lengths, "exact")
 
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """Sample (states, one-hot observations) — reference hmm.py:213-245 (not on the hot

@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .autograd import GmmLogProb, needs_grad
+from .autograd import GmmLogProb, valid_frames, needs_grad
 from .hmm import HMMPyTorch
 from .utils import create_left_to_right_matrix, create_transition_matrix
 
@@ -87,8 +87,11 @@ class HMMLayer(nn.Module):
         return self._hmm
 
     # -- forward (hmm_layer.py:91-142) -------------------------------------------------
-    def forward(self, x: torch.Tensor,
-                return_alignment: bool = False) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    def forward(self, x: torch.Tensor, return_alignment: bool = False,
+                lengths=None) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """lengths (None = every sequence has T frames): one length per sequence of a padded batch
+        (HMMPyTorch.forward_backward).  The frames past a sequence's length are never read; their
+        posterior / one-hot rows are zero and the alignment is -1 there."""
         if self.apply_sigmoid:
             x = torch.sigmoid(x)
         if x.dim() == 2:
@@ -97,36 +100,51 @@ class HMMLayer(nn.Module):
         if K != self.num_states:
             raise ValueError(f"Input feature dim {K} must match num_states {self.num_states}")
         hmm = self._get_hmm()
+        lens = ops.active_lengths(lengths, B, T, K)
+        valid = None if lens is None else valid_frames(lens, T, x.device)
         if self.training:
-            posteriors = hmm.posteriors(x)
+            posteriors = hmm.posteriors(x, lens)
         elif self.viterbi_inference:
-            states, _ = hmm.viterbi_decode(x)
-            posteriors = F.one_hot(states, num_classes=self.num_states).float()
+            states, _ = hmm.viterbi_decode(x, lens)
+            if valid is None:
+                posteriors = F.one_hot(states, num_classes=self.num_states).float()
+            else:
+                posteriors = F.one_hot(states.clamp(min=0), num_classes=self.num_states).float() * valid[..., None]
         else:
-            posteriors = hmm.posteriors(x)
+            posteriors = hmm.posteriors(x, lens)
         if return_alignment and not self.training:
-            alignment = states if self.viterbi_inference else torch.argmax(posteriors, dim=-1)
+            if self.viterbi_inference:
+                alignment = states
+            else:
+                alignment = torch.argmax(posteriors, dim=-1)
+                if valid is not None:
+                    alignment = torch.where(valid, alignment, torch.full_like(alignment, -1))
             return posteriors, alignment
         return posteriors
 
-    def compute_loss(self, observations: torch.Tensor,
-                     target_alignment: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def compute_loss(self, observations: torch.Tensor, target_alignment: Optional[torch.Tensor] = None,
+                     lengths=None) -> torch.Tensor:
         """Cross-entropy on posteriors when a target alignment is given, else -mean of
-        compute_likelihood (hmm_layer.py:144-173)."""
+        compute_likelihood (hmm_layer.py:144-173).  With lengths the cross-entropy runs over the
+        valid frames only and the likelihood of sequence b is that of its lengths[b] frames."""
         hmm = self._get_hmm()
         if target_alignment is not None:
-            posteriors = self.forward(observations)
+            posteriors = self.forward(observations, lengths=lengths)
+            lens = ops.active_lengths(lengths, posteriors.shape[0], posteriors.shape[1], self.num_states)
+            if lens is not None:
+                valid = valid_frames(lens, posteriors.shape[1], posteriors.device)
+                return F.cross_entropy(posteriors[valid], target_alignment.reshape(valid.shape)[valid])
             return F.cross_entropy(posteriors.view(-1, self.num_states), target_alignment.view(-1))
         if self.apply_sigmoid:
             observations = torch.sigmoid(observations)
-        return -hmm.compute_likelihood(observations).mean()
+        return -hmm.compute_likelihood(observations, lengths).mean()
 
-    def align(self, observations: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def align(self, observations: torch.Tensor, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(states, log_delta) by Viterbi (hmm_layer.py:175-191)."""
         hmm = self._get_hmm()
         if self.apply_sigmoid:
             observations = torch.sigmoid(observations)
-        return hmm.viterbi_decode(observations)
+        return hmm.viterbi_decode(observations, lengths)
 
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         return self._get_hmm().sample(seq_length, batch_size)
@@ -186,14 +204,24 @@ class GaussianHMMLayer(nn.Module):
         lv = _gaussian_component_params(self.log_scales.detach(), self.covariance_type, D)
         return ops.gmm_diag_logprob(observations.detach(), self.means.detach().unsqueeze(1), lv, log_w, 0)
 
-    def forward(self, observations: torch.Tensor) -> torch.Tensor:
-        observation_probs = torch.exp(self._compute_gaussian_log_probs(observations))
-        return self.hmm_layer(observation_probs)
+    def _observation_probs(self, observations, lengths):
+        """exp of the Gaussian log-densities.  With lengths the padded frames are zeroed first
+        (selected, not multiplied), so whatever they hold stays out of the parameters' gradients."""
+        if lengths is not None:
+            B, T = observations.shape[:2]
+            lens = ops.active_lengths(lengths, B, T, self.num_states)
+            if lens is not None:
+                valid = valid_frames(lens, T, observations.device)
+                observations = torch.where(valid[..., None], observations, torch.zeros_like(observations))
+        return torch.exp(self._compute_gaussian_log_probs(observations))
 
-    def compute_loss(self, observations: torch.Tensor) -> torch.Tensor:
-        observation_probs = torch.exp(self._compute_gaussian_log_probs(observations))
+    def forward(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
+        return self.hmm_layer(self._observation_probs(observations, lengths), lengths=lengths)
+
+    def compute_loss(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
+        observation_probs = self._observation_probs(observations, lengths)
         hmm = self.hmm_layer._get_hmm()
-        return -hmm.compute_likelihood(observation_probs).mean()
+        return -hmm.compute_likelihood(observation_probs, lengths).mean()
 
     def extra_repr(self) -> str:
         return (f"num_states={self.num_states}, feature_dim={self.feature_dim}, "

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .autograd import GmmLogProb, ViterbiScore, needs_grad
+from .autograd import GmmLogProb, ViterbiScore, needs_grad, valid_frames
 
 
 class MixtureGaussianHMMLayer(nn.Module):
@@ -168,16 +168,20 @@ class MixtureGaussianHMMLayer(nn.Module):
                                         tuple(log_transitions.shape), plan)
         return plan
 
-    def _viterbi_decode(self, obs_log_probs: torch.Tensor,
-                        log_transitions: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _viterbi_decode(self, obs_log_probs: torch.Tensor, log_transitions: torch.Tensor,
+                        lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(states (B,T), max_j delta_{T-1}[j] (B,)) with delta_0 = lp_0 - log S
-        (mixture_gaussian.py:290-338)."""
+        (mixture_gaussian.py:290-338).  lengths (ops.active_lengths): sequence b is its first
+        lengths[b] frames, the score max_j delta[lengths[b] - 1][j], states -1 past it."""
         S = obs_log_probs.shape[-1]
         init = -(torch.zeros(S, device=obs_log_probs.device) + math.log(S))
         plan = self._transition_plan(log_transitions)
         if needs_grad(obs_log_probs, log_transitions):
             # the score's gradient follows the decoded path (the reference's max-plus autograd)
-            return ViterbiScore.apply(obs_log_probs, log_transitions, init, plan)
+            return ViterbiScore.apply(obs_log_probs, log_transitions, init, plan, lengths)
+        if lengths is not None:
+            states, _, final = ops.viterbi_ragged(obs_log_probs, log_transitions, init, ops.OBS_LOG, lengths)
+            return states, final
         states, _, final = ops.viterbi(obs_log_probs, log_transitions, init, ops.OBS_LOG, plan)
         return states, final
 
@@ -218,8 +222,16 @@ class MixtureGaussianHMMLayer(nn.Module):
         self.refresh_tables()
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def forward(self, observations: torch.Tensor,
-                return_log_probs: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    def forward(self, observations: torch.Tensor, return_log_probs: bool = False,
+                lengths=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """lengths (None = every sequence has T frames): one length per sequence of a padded batch.
+        The frames past a sequence's length do not enter its decode and get state -1; the score is
+        max_j delta[lengths[b] - 1][j]."""
+        lens = ops.active_lengths(lengths, observations.shape[0], observations.shape[1], self.num_states)
+        if lens is not None:
+            # padded frames are zeroed (selected, not multiplied) before they are scored
+            valid = valid_frames(lens, observations.shape[1], observations.device)
+            observations = torch.where(valid[..., None], observations, torch.zeros_like(observations))
         if self.covariance_type != "full" and not needs_grad(observations, *self.parameters()):
             # inference: the cached tables (_inference_tables), the GMM scorer, then the decode;
             # the same bits as get_observation_log_probs followed by _viterbi_decode
@@ -230,11 +242,14 @@ class MixtureGaussianHMMLayer(nn.Module):
             with torch.no_grad():
                 log_T, log_w, init, plan = self._inference_tables(observations.device)
                 lp = ops.gmm_diag_logprob(observations, self.means, self._component_log_vars(), log_w, 1)
-                states, _, scores = ops.viterbi(lp, log_T, init, ops.OBS_LOG, plan)
+                if lens is not None:
+                    states, _, scores = ops.viterbi_ragged(lp, log_T, init, ops.OBS_LOG, lens)
+                else:
+                    states, _, scores = ops.viterbi(lp, log_T, init, ops.OBS_LOG, plan)
             return (states, scores) if return_log_probs else (states, None)
         log_transitions = self._safe_log(self.get_transition_matrix())
         obs_log_probs = self.get_observation_log_probs(observations)
-        states, scores = self._viterbi_decode(obs_log_probs, log_transitions)
+        states, scores = self._viterbi_decode(obs_log_probs, log_transitions, lens)
         return (states, scores) if return_log_probs else (states, None)
 
     def get_model_info(self) -> dict:

@@ -8,6 +8,9 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.forward_backward(obs, log_P, log_p0, obs_mode, out_mask)
       -> (posterior, forward, backward, loglik, lik_ref)
   torch.ops.hmm355.viterbi(obs, log_P, init, obs_mode) -> (states, log_delta, final_score)
+  torch.ops.hmm355.forward_backward_ragged(obs, log_P, log_p0, obs_mode, lengths, out_mask, log_beta_T)
+      -> (posterior, forward, backward, loglik, lik_ref)     sequence b = obs[b, :lengths[b]]
+  torch.ops.hmm355.viterbi_ragged(obs, log_P, init, obs_mode, lengths) -> (states, log_delta, final_score)
   torch.ops.hmm355.gmm_diag_logprob(x, means, log_vars, log_w, mix_lse) -> log_probs
   torch.ops.hmm355.hsmm_viterbi(lp, dur_lp, log_T) -> (states, scores)
   torch.ops.hmm355.hsmm_forward_backward(lp, dur_lp, log_T, log_init, want_gamma=, want_dur=,
@@ -268,6 +271,136 @@ def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
 def _(obs, log_P, init, obs_mode, plan=None, follow=None, wide=None):
     B, T, N = obs.shape
     return (obs.new_empty((B, T), dtype=torch.int64), obs.new_empty((B, T, N)), obs.new_empty(B))
+
+
+# ------------------------------------------------------- padded batches with lengths
+def ragged_lengths(lengths, B: int, T: int, N: Optional[int] = None) -> Tensor:
+    """Checks the per-sequence lengths of a padded (B,T,N) batch on the host (ValueError) and
+    returns them as a CPU int64 tensor (B).  Accepts a tensor on any device, a list or a numpy
+    array; needs exactly B integer values in [1, T].  The lengths are read on the host: the call's
+    one synchronisation.  With N given, more than 256 states are rejected: the ragged form is one
+    workgroup per sequence (csrc/ragged.hip)."""
+    if N is not None and N > NARROW_MAX_STATES:
+        raise ValueError(f"per-sequence lengths are supported for at most {NARROW_MAX_STATES} states; got {N}")
+    t = torch.as_tensor(lengths)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"lengths must hold integers; got {t.dtype}")
+    if t.numel() != B:
+        raise ValueError(f"lengths must hold one length per sequence ({B}); got {tuple(t.shape)}")
+    host = t.detach().reshape(B).to("cpu", torch.int64)
+    if B and (int(host.min()) < 1 or int(host.max()) > T):
+        raise ValueError(f"lengths must lie in [1, {T}]; got {host.tolist()}")
+    return host
+
+
+def active_lengths(lengths, B: int, T: int, N: Optional[int] = None) -> Optional[Tensor]:
+    """The checked lengths (ragged_lengths) when they shorten a sequence, None when `lengths` is
+    None or every length is T: the callers' `lengths=None` path, bit for bit."""
+    if lengths is None:
+        return None
+    host = ragged_lengths(lengths, B, T, N)
+    return None if bool((host == T).all()) else host
+
+
+def _equal_length(host: Tensor) -> Optional[int]:
+    """The common length when every sequence has the same one (B == 1 included), else None."""
+    if host.numel() == 0:
+        return None
+    first = int(host[0])
+    return first if bool((host == first).all()) else None
+
+
+def _pad_frames(x: Tensor, T: int, fill) -> Tensor:
+    """x (B,L,...) padded with `fill` to T frames (x itself when L == T)."""
+    if x.shape[1] == T:
+        return x
+    out = x.new_full((x.shape[0], T) + tuple(x.shape[2:]), fill)
+    out[:, : x.shape[1]] = x
+    return out
+
+
+@torch.library.custom_op("hmm355::forward_backward_ragged", mutates_args=())
+def forward_backward_ragged(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int, lengths: Tensor,
+                            out_mask: int,
+                            log_beta_T: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """forward_backward of a padded batch: sequence b is obs[b, :lengths[b]].  Outputs as
+    forward_backward; posterior / forward / backward are 0 in frames >= lengths[b], which are
+    never read.  Dispatch is from the input alone: equal lengths (B == 1 included) run the tuned
+    chains on obs[:, :L] with today's speed and bits, unequal ones csrc/ragged.hip.  log_beta_T
+    (B,N): the terminal backward vector at frame lengths[b] - 1 (always the ragged form)."""
+    B, T, N = obs.shape
+    host = ragged_lengths(lengths, B, T, N)
+    nat.require_gpu(obs, log_P, log_p0, log_beta_T)
+    out_mask &= FB_POSTERIOR | FB_FORWARD | FB_BACKWARD
+    L0 = _equal_length(host)
+    if log_beta_T is None and (B == 0 or L0 is not None):
+        post, fwd, bwd, loglik, lik_ref = forward_backward(obs[:, :L0] if B else obs, log_P, log_p0, obs_mode, out_mask)
+        pad = lambda x, bit: _pad_frames(x, T, 0.0) if out_mask & bit else x
+        return pad(post, FB_POSTERIOR), pad(fwd, FB_FORWARD), pad(bwd, FB_BACKWARD), loglik, lik_ref
+    obs, log_P, log_p0 = _f32c(obs), _f32c(log_P), _f32c(log_p0)
+    lbt = None if log_beta_T is None else _f32c(log_beta_T)
+    dev = obs.device
+    lens = host.to(torch.int32).to(dev)
+    L = nat.lib()
+    post = torch.empty((B, T, N) if out_mask & FB_POSTERIOR else _EMPTY, device=dev)
+    fwd = torch.empty((B, T, N) if out_mask & FB_FORWARD else _EMPTY, device=dev)
+    bwd = torch.empty((B, T, N) if out_mask & FB_BACKWARD else _EMPTY, device=dev)
+    loglik = torch.empty(B, device=dev)
+    lik_ref = torch.empty(B, device=dev)
+    ws = _workspace(L.hmm355_fb_workspace_bytes(B, T, N), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_forward_backward_ragged_f32(
+            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(lbt), nat.ptr(lens), B, T, N, out_mask,
+            nat.ptr(post) if out_mask & FB_POSTERIOR else None,
+            nat.ptr(fwd) if out_mask & FB_FORWARD else None,
+            nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
+            nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return post, fwd, bwd, loglik, lik_ref
+
+
+@forward_backward_ragged.register_fake
+def _(obs, log_P, log_p0, obs_mode, lengths, out_mask, log_beta_T=None):
+    B, T, N = obs.shape
+    mk = lambda bit: obs.new_empty((B, T, N) if out_mask & bit else _EMPTY, dtype=torch.float32)
+    return (mk(FB_POSTERIOR), mk(FB_FORWARD), mk(FB_BACKWARD), obs.new_empty(B, dtype=torch.float32),
+            obs.new_empty(B, dtype=torch.float32))
+
+
+@torch.library.custom_op("hmm355::viterbi_ragged", mutates_args=())
+def viterbi_ragged(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
+                   lengths: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """viterbi of a padded batch: sequence b is obs[b, :lengths[b]].  (states, log_delta,
+    final_score) as viterbi, the valid frames bit-identical to a decode of the slice alone;
+    frames >= lengths[b] are never read and get states = -1, log_delta = -inf.  final_score[b] =
+    max_j delta[lengths[b] - 1][j].  Equal lengths run the tuned chains on obs[:, :L], unequal
+    ones csrc/ragged.hip."""
+    B, T, N = obs.shape
+    host = ragged_lengths(lengths, B, T, N)
+    nat.require_gpu(obs, log_P, init)
+    L0 = _equal_length(host)
+    if B == 0 or L0 is not None:
+        states, delta, final = viterbi(obs[:, :L0] if B else obs, log_P, init, obs_mode)
+        return _pad_frames(states, T, -1), _pad_frames(delta, T, float("-inf")), final
+    obs, log_P, init = _f32c(obs), _f32c(log_P), _f32c(init)
+    dev = obs.device
+    lens = host.to(torch.int32).to(dev)
+    L = nat.lib()
+    states = torch.empty((B, T), dtype=torch.int64, device=dev)
+    delta = torch.empty((B, T, N), device=dev)
+    final = torch.empty(B, device=dev)
+    ws = _workspace(L.hmm355_viterbi_ragged_workspace_bytes(B, T, N, obs_mode), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_viterbi_ragged_f32(
+            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(lens), B, T, N, nat.ptr(states),
+            nat.ptr(delta), nat.ptr(final), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return states, delta, final
+
+
+@viterbi_ragged.register_fake
+def _(obs, log_P, init, obs_mode, lengths):
+    B, T, N = obs.shape
+    return (obs.new_empty((B, T), dtype=torch.int64), obs.new_empty((B, T, N), dtype=torch.float32),
+            obs.new_empty(B, dtype=torch.float32))
 
 
 # ------------------------------------------------------------------- GMM emission
