@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -293,6 +293,45 @@ int hmm355_forward_backward_ragged_f32(const float* obs, int obs_mode, const flo
                                        float* posterior, float* forward, float* backward,
                                        float* loglik, float* lik_ref, void* workspace,
                                        size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Posterior path sampling (csrc/ffbs.hip), 1 <= N <= 256: the backward-sampling pass of
+ * forward-filter backward-sample.  Draws K state paths per sequence from p(z | x), given the scaled
+ * forward rows a forward-backward call leaves in its workspace and uniform numbers from the caller
+ * (no random number generation in the kernel).
+ *   fwd       (B,T) rows of ld floats, ld >= N: row (b,t) is proportional to alpha_t of sequence b
+ *             (non-negative entries, any positive scale: the kernel forms the total itself).
+ *             Columns N .. ld-1 are never read.  The U piece of hmm355_fb_workspace_layout with
+ *             ld = NP (N padded to 64/128/256) is the intended input; keep it by calling
+ *             hmm355_forward_backward_plan_f32 without the HMM355_FB_PAIR / _PLAN_BANDED hints, or
+ *             hmm355_forward_backward_ragged_f32.
+ *   log_P     (N,N); A = exp(log_P) in fp32
+ *   lengths   (B) int32 or NULL (every sequence has T frames); clamped to [1, T] as read
+ *   uniforms  (B,K,T) numbers in [0, 1)
+ *   states    (B,K,T) int64 out
+ * With L = lengths[b], for each (b,k) and t = L-1 down to 0:
+ *   w[i]  = fwd[b,t,i] at t = L-1, else fwd[b,t,i] * A[i][z_{t+1}]
+ *   C[i]  = the inclusive prefix sum of w in ascending i (fp32, any association),
+ *           total = C[N-1], r = uniforms[b,k,t] * total
+ *   z_t   = the smallest i with C[i] > r; if there is none (u * total rounded up to total) the
+ *           largest i with w[i] > 0.  The chosen state always has w[z_t] > 0: a search that lands
+ *           on a zero weight (a tree-shaped scan is not exactly monotone from lane to lane) moves
+ *           to the nearest positive-weight index at or below it, else the nearest above it.
+ *   A total that is not positive and finite: z_t = the first index maximising fwd[b,t,.] (state 0
+ *   for a row of zeros).  Every state of a valid frame lies in [0, N-1].
+ *   Frames t >= L get state -1; their fwd rows and uniforms are never read.
+ * One wave per (b,k) chain; each launch is complete on its own (no waits between workgroups, no
+ * atomics): the same inputs give the same states.
+ * workspace >= hmm355_ffbs_workspace_bytes(N): exp(log_P)^T (NP,NP), built once per call.
+ * Status: HMM355_E_STATES for N outside [1, 256] (the size query returns 0); HMM355_E_SHAPE for
+ * T < 1, K < 1 or a size that overflows; HMM355_E_ARG for ld < N, a null pointer (lengths
+ * excepted) or B < 0; HMM355_E_WORKSPACE for a short workspace; B == 0 is a no-op.  Every check
+ * comes before any launch.
+ * ------------------------------------------------------------------------------ */
+size_t hmm355_ffbs_workspace_bytes(int N);
+int hmm355_ffbs_f32(const float* fwd, int ld, const float* log_P, const int* lengths /* (B) or NULL */,
+                    const float* uniforms /* (B,K,T) */, int B, int T, int N, int K,
+                    int64_t* states /* (B,K,T) */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Diagonal-covariance Gaussian-mixture emission scorer.  Replaces

@@ -40,3 +40,7 @@ from .hsmm import DurationConstrainedHMM
 from .utils import compute_state_durations, create_duration_constrained_matrix
 
 __all__ += ["DurationConstrainedHMM", "compute_state_durations", "create_duration_constrained_matrix"]
+
+from .ops import posterior_sample
+
+__all__ += ["posterior_sample"]

@@ -73,6 +73,7 @@ EXPORTS = (
     "hmm355_forced_workspace_bytes", "hmm355_forced_f32", "hmm355_forced_grad_f32",
     "hmm355_durforced_workspace_bytes", "hmm355_durforced_f32", "hmm355_durforced_grad_f32",
     "hmm355_viterbi_ragged_workspace_bytes", "hmm355_viterbi_ragged_f32", "hmm355_forward_backward_ragged_f32",
+    "hmm355_ffbs_workspace_bytes", "hmm355_ffbs_f32",
 )
 
 _lib = None
@@ -189,6 +190,8 @@ def lib():
     L.hmm355_viterbi_ragged_f32.restype = I
     L.hmm355_forward_backward_ragged_f32.argtypes = [P, I, P, P, P, P, I, I, I, U, P, P, P, P, P, P, S, P]
     L.hmm355_forward_backward_ragged_f32.restype = I
+    L.hmm355_ffbs_workspace_bytes.argtypes, L.hmm355_ffbs_workspace_bytes.restype = [I], S
+    L.hmm355_ffbs_f32.argtypes, L.hmm355_ffbs_f32.restype = [P, I, P, P, P, I, I, I, I, P, P, S, P], I
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // hmm355 — C ABI housekeeping (error strings, version).
 #include "common.h"
 
-HMM355_API int hmm355_version(void) { return 10; }
+HMM355_API int hmm355_version(void) { return 11; }
 
 HMM355_API const char* hmm355_strerror(int code) {
   switch (code) {

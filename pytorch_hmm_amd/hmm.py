@@ -165,6 +165,66 @@ class HMMPyTorch(HMM):
         (what compute_likelihood would return without exp() underflow)."""
         return self._likelihood(observations, lengths, "exact")
 
+    def sample_posterior(self, observations: torch.Tensor, num_samples: int = 1, lengths=None,
+                         generator: Optional[torch.Generator] = None, return_log_prob: bool = False):
+        """Extension: num_samples state paths per sequence drawn from p(z | x) by forward-filter
+        backward-sample (ops.posterior_sample, csrc/ffbs.hip): (B,K,T) int64, (K,T) for 2-D input,
+        -1 in the frames past a sequence's length.  Unlike per-frame draws from posteriors() these
+        are paths: consecutive states follow the transition matrix.  generator: a torch.Generator
+        on the observations' device for the uniform numbers (None: the default one).  Takes no
+        gradients (the inputs are detached).  return_log_prob=True also returns log p(z | x) of
+        every drawn path (path_log_posterior), (B,K) or (K)."""
+        obs, squeeze = self._as_batch(observations)
+        assert obs.shape[-1] == self.K, f"Observation dim {obs.shape[-1]} must match model states {self.K}"
+        log_P, log_p0, plan = self._device_params(obs.device)
+        states, _ = ops.posterior_sample(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB, num_samples,
+                                         lengths=lengths, plan=plan, generator=generator)
+        if not return_log_prob:
+            return states.squeeze(0) if squeeze else states
+        with torch.no_grad():
+            lp = self.path_log_posterior(obs, states, lengths)
+        return (states.squeeze(0), lp.squeeze(0)) if squeeze else (states, lp)
+
+    def _path_terms(self, obs, states, lengths):
+        """(log joint (B,K), log-likelihood (B)) of the paths `states` (B,K,T): log p0[z_0] + sum of
+        log P[z_{t-1}, z_t] + sum of log(obs + 1e-8)[t, z_t] over the valid frames, by torch gathers."""
+        B, T, K = obs.shape
+        log_P, log_p0, _ = self._device_params(obs.device)
+        log_P, log_p0, obs = log_P.detach(), log_p0.detach(), obs.detach()
+        lens = ops.active_lengths(lengths, B, T, K)
+        valid = torch.ones(B, T, dtype=torch.bool, device=obs.device) if lens is None else (
+            torch.arange(T, device=obs.device)[None, :] < lens.to(obs.device)[:, None])
+        z = states.to(obs.device).clamp(min=0)                            # padded frames: any state, masked below
+        on = valid[:, None, :]                                            # (B,1,T)
+        le = torch.log(obs + 1e-8)                                        # the reference's emissions (hmm.py:86)
+        emis = torch.gather(le[:, None].expand(B, z.shape[1], T, K), 3, z.unsqueeze(-1)).squeeze(-1)
+        # the T terms are summed in fp64 (the fp32 terms themselves are the model's)
+        joint = torch.where(on, emis, torch.zeros_like(emis)).sum(-1, dtype=torch.float64) + log_p0[z[:, :, 0]]
+        if T > 1:
+            trans = log_P[z[:, :, :-1], z[:, :, 1:]]
+            joint = joint + torch.where(on[:, :, 1:], trans, torch.zeros_like(trans)).sum(-1, dtype=torch.float64)
+        return joint.to(torch.float32), self.log_likelihood(obs, lengths)
+
+    def path_log_posterior(self, observations: torch.Tensor, states: torch.Tensor, lengths=None) -> torch.Tensor:
+        """Extension: log p(z | x) = log p0[z_0] + sum log P[z_{t-1}, z_t] + sum log e_t[z_t] -
+        log_likelihood of the state paths `states` ((B,K,T) -> (B,K), or (B,T) -> (B); with 2-D
+        observations (K,T) -> (K) or (T) -> a scalar).  Emissions are the reference's
+        log(obs + 1e-8); frames past a sequence's length are ignored (any value, -1 included)."""
+        obs, squeeze = self._as_batch(observations)
+        assert obs.shape[-1] == self.K, f"Observation dim {obs.shape[-1]} must match model states {self.K}"
+        st = states.unsqueeze(0) if squeeze else states
+        single = st.dim() == 2
+        if single:
+            st = st.unsqueeze(1)
+        if st.dim() != 3 or st.shape[0] != obs.shape[0] or st.shape[2] != obs.shape[1]:
+            raise ValueError(f"states must be (B, K, T) or (B, T) for observations {tuple(obs.shape)}; "
+                             f"got {tuple(states.shape)}")
+        joint, loglik = self._path_terms(obs, st, lengths)
+        out = joint - loglik[:, None]
+        if single:
+            out = out.squeeze(1)
+        return out.squeeze(0) if squeeze else out
+
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """Sample (states, one-hot observations) — reference hmm.py:213-245 (not on the hot
         path; plain torch sampling on the parameters' device)."""

@@ -146,6 +146,16 @@ class HMMLayer(nn.Module):
             observations = torch.sigmoid(observations)
         return hmm.viterbi_decode(observations, lengths)
 
+    def sample_alignment(self, x: torch.Tensor, num_samples: int = 1, lengths=None,
+                         generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """num_samples alignments per sequence drawn from p(z | x) (HMMPyTorch.sample_posterior) on
+        the emissions align() decodes: (B,K,T) int64, (K,T) for 2-D input, -1 in the frames past a
+        sequence's length.  No gradients."""
+        hmm = self._get_hmm()
+        if self.apply_sigmoid:
+            x = torch.sigmoid(x)
+        return hmm.sample_posterior(x, num_samples, lengths, generator)
+
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         return self._get_hmm().sample(seq_length, batch_size)
 
@@ -222,6 +232,15 @@ class GaussianHMMLayer(nn.Module):
         observation_probs = self._observation_probs(observations, lengths)
         hmm = self.hmm_layer._get_hmm()
         return -hmm.compute_likelihood(observation_probs, lengths).mean()
+
+    def sample_alignment(self, x: torch.Tensor, num_samples: int = 1, lengths=None,
+                         generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """num_samples alignments per sequence drawn from p(z | x) under the Gaussian emissions
+        (HMMLayer.sample_alignment on the observation probabilities): (B,K,T) int64, -1 in the
+        frames past a sequence's length.  No gradients."""
+        with torch.no_grad():
+            probs = self._observation_probs(x, lengths)
+        return self.hmm_layer.sample_alignment(probs, num_samples, lengths, generator)
 
     def extra_repr(self) -> str:
         return (f"num_states={self.num_states}, feature_dim={self.feature_dim}, "

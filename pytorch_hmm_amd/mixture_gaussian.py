@@ -252,6 +252,23 @@ class MixtureGaussianHMMLayer(nn.Module):
         states, scores = self._viterbi_decode(obs_log_probs, log_transitions, lens)
         return (states, scores) if return_log_probs else (states, None)
 
+    def sample_alignment(self, x: torch.Tensor, num_samples: int = 1, lengths=None,
+                         generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """num_samples alignments per sequence drawn from p(z | x) (ops.posterior_sample with
+        OBS_LOG) under the model forward() decodes: the mixture emission log-probabilities, the log
+        transitions and the uniform initial vector of its Viterbi.  (B,K,T) int64, -1 in the frames
+        past a sequence's length.  No gradients."""
+        lens = ops.active_lengths(lengths, x.shape[0], x.shape[1], self.num_states)
+        if lens is not None:
+            valid = valid_frames(lens, x.shape[1], x.device)
+            x = torch.where(valid[..., None], x, torch.zeros_like(x))
+        with torch.no_grad():
+            log_T, _, init, plan = self._inference_tables(x.device)
+            lp = self.get_observation_log_probs(x)
+            states, _ = ops.posterior_sample(lp, log_T, init, ops.OBS_LOG, num_samples, lengths=lens, plan=plan,
+                                             generator=generator)
+        return states
+
     def get_model_info(self) -> dict:
         total = sum(p.numel() for p in self.parameters())
         trainable = sum(p.numel() for p in self.parameters() if p.requires_grad)

@@ -40,6 +40,7 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.durforced_grad(begin, F, Bend, Bbeg, frame_shift, loglik_shifted, log_probs, state_ids,
                                   input_lengths, state_lengths, dur_lp, want_gamma=, want_grad=, want_dur=)
       -> (gamma, grad_log_probs, grad_dur_lp)
+  torch.ops.hmm355.ffbs(fwd, log_P, uniforms, lengths) -> states (B,K,T)     posterior path samples
 """
 from typing import Optional, Tuple
 
@@ -1453,3 +1454,96 @@ def _(emission_log_probs, log_transitions, min_duration, max_duration, penalty_w
             emission_log_probs.new_empty(B, dtype=torch.float32),
             emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.float32),
             emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.int32))
+
+
+# ------------------------------------------------------------------ posterior path sampling
+def _row_stride(x: Tensor) -> Optional[int]:
+    """ld when the rows of x (B,T,N) are contiguous and row (b,t) starts (b*T + t) * ld floats into
+    x with ld >= N (a [..., :N] view of a (B,T,NP) buffer, or a contiguous tensor), else None."""
+    B, T, N = x.shape
+    if N > 1 and x.stride(2) != 1:
+        return None
+    ld = x.stride(1) if T > 1 else (x.stride(0) if B > 1 else N)
+    if ld < N or (T > 1 and B > 1 and x.stride(0) != T * ld):
+        return None
+    return ld
+
+
+@torch.library.custom_op("hmm355::ffbs", mutates_args=())
+def ffbs(fwd: Tensor, log_P: Tensor, uniforms: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    """The backward-sampling pass of forward-filter backward-sample (hmm355_ffbs_f32,
+    csrc/ffbs.hip; the draw is spelled out in include/hmm355.h).  fwd (B,T,N): rows proportional
+    to alpha_t, non-negative, any positive scale -- the U rows autograd._run_fb returns are the
+    intended input.  A strided view with a contiguous last dimension is read in place (its row
+    stride is the C ABI's ld); anything else is copied.  log_P (N,N), uniforms (B,K,T) in [0, 1),
+    lengths (B) or None.  Returns states (B,K,T) int64, -1 in frames >= lengths[b]; those frames'
+    rows and uniforms are never read.  1 <= N <= 256."""
+    if fwd.dim() != 3:
+        raise ValueError(f"fwd must be (B, T, N); got {tuple(fwd.shape)}")
+    B, T, N = fwd.shape
+    if N > NARROW_MAX_STATES:
+        raise ValueError(f"posterior path sampling supports at most {NARROW_MAX_STATES} states; got {N}")
+    if tuple(log_P.shape) != (N, N):
+        raise ValueError(f"log_P must be ({N}, {N}); got {tuple(log_P.shape)}")
+    if uniforms.dim() != 3 or uniforms.shape[0] != B or uniforms.shape[2] != T or uniforms.shape[1] < 1:
+        raise ValueError(f"uniforms must be (B, K, T) = ({B}, K >= 1, {T}); got {tuple(uniforms.shape)}")
+    K = uniforms.shape[1]
+    host = None if lengths is None else ragged_lengths(lengths, B, T, N)
+    nat.require_gpu(fwd, log_P, uniforms)
+    dev = fwd.device
+    fwd = fwd.detach()
+    if fwd.dtype != torch.float32:
+        fwd = fwd.to(torch.float32)
+    ld = _row_stride(fwd)
+    if ld is None:
+        fwd = fwd.contiguous()
+        ld = N
+    log_P, uniforms = _f32c(log_P.detach()), _f32c(uniforms.detach())
+    states = torch.empty((B, K, T), dtype=torch.int64, device=dev)
+    if B == 0 or T == 0:
+        return states
+    lens = None if host is None else host.to(torch.int32).to(dev)
+    L = nat.lib()
+    ws = _workspace(L.hmm355_ffbs_workspace_bytes(N), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_ffbs_f32(nat.ptr(fwd), int(ld), nat.ptr(log_P), nat.ptr(lens), nat.ptr(uniforms), B, T, N, K,
+                                    nat.ptr(states), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return states
+
+
+@ffbs.register_fake
+def _(fwd, log_P, uniforms, lengths=None):
+    B, T, _ = fwd.shape
+    return fwd.new_empty((B, uniforms.shape[1], T), dtype=torch.int64)
+
+
+def posterior_sample(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int, num_samples: int, *,
+                     uniforms: Optional[Tensor] = None, lengths=None, plan: Optional[Tensor] = None,
+                     generator: Optional[torch.Generator] = None) -> Tuple[Tensor, Tensor]:
+    """num_samples state paths per sequence drawn from p(z | x): (states (B,K,T) int64, loglik (B)).
+    One forward-backward call that keeps its scaled forward rows U (the plan entry point without the
+    FB_PAIR / FB_PLAN_BANDED hints, the ragged one when the lengths differ: autograd._run_fb),
+    then ffbs on them.  uniforms (B,K,T) in [0, 1), or None to draw torch.rand with `generator`.
+    Padded frames (t >= lengths[b]) get state -1.  No gradients: the inputs are detached."""
+    from . import autograd
+    if obs.dim() != 3:
+        raise ValueError(f"obs must be (B, T, N); got {tuple(obs.shape)}")
+    B, T, N = obs.shape
+    K = int(num_samples)
+    if K < 1:
+        raise ValueError(f"num_samples must be at least 1; got {num_samples}")
+    if N > NARROW_MAX_STATES:
+        raise ValueError(f"posterior path sampling supports at most {NARROW_MAX_STATES} states; got {N}")
+    if uniforms is not None and tuple(uniforms.shape) != (B, K, T):
+        raise ValueError(f"uniforms must be (B, K, T) = ({B}, {K}, {T}); got {tuple(uniforms.shape)}")
+    lens = active_lengths(lengths, B, T, N)
+    nat.require_gpu(obs, log_P, log_p0, uniforms)
+    dev = obs.device
+    if uniforms is None:
+        uniforms = torch.rand((B, K, T), device=dev, generator=generator)
+    obs_c, lP, l0 = (_f32c(t.detach()) for t in (obs, log_P, log_p0))
+    if B == 0:
+        return torch.empty((0, K, T), dtype=torch.int64, device=dev), torch.empty(0, device=dev)
+    _, loglik, _, U, *_ = autograd._run_fb(obs_c, lP, l0, obs_mode, plan=None if lens is not None else plan,
+                                           lengths=lens)
+    return ffbs(U, lP, uniforms, lens), loglik
