@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]; emission statistics hmm355_gmm_stats_f32 C [1, 256], S*C <= 65536) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -354,6 +354,45 @@ int hmm355_gmm_diag_logprob_f32(const float* x, const float* means, const float*
                                 const float* log_w, int B, int T, int D, int S, int C,
                                 int mix_lse, float* out, void* workspace,
                                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Occupancy-weighted sufficient statistics of the diagonal Gaussian (mixture) emissions
+ * (csrc/emstats.hip): the emission half of the Baum-Welch E-step (pytorch_hmm_amd/em.py).  The
+ * reference has no counterpart (it trains by autograd only).
+ *   x (B,T,D); weight (B,T,S), any sign (EM passes the state posteriors); means, log_vars (S,C,D);
+ *   log_w (S,C) or NULL for 0; lengths (B) int32 or NULL (every sequence has T frames).
+ * With comp[b,t,s,c] the scorer's component score above (-0.5*(...) + log_w) and r the softmax of
+ * comp over c, shifted by its maximum (r = 0 for every c of a state whose components are all -inf;
+ * r = 1 when mix_lse == 0, which requires C == 1), and w[b,t,s,c] = weight[b,t,s] * r[b,t,s,c]:
+ *   occ (S,C)   = sum_{b, t < lengths[b]} w
+ *   sx  (S,C,D) = sum w * (x - mu)
+ *   sxx (S,C,D) = sum w * (x - mu)^2
+ * all fp32; any of the three may be NULL and is then skipped.  The moments are centred on the
+ * means passed in: mu' = mu + sx/occ and var' = sxx/occ - (sx/occ)^2 have none of the cancellation
+ * of raw second moments.  A component with log_w = -inf gets exactly 0 in all three outputs.
+ * Frames at t >= lengths[b] are never read, in x or in weight (their values are selected out, not
+ * multiplied by a mask).  Precision: the quadratic form, the products and the sums are fp64; the
+ * exponentials of the softmax are fp32 (expf/logf), each workgroup's partial sum is rounded to fp32
+ * once and the partial sums are added in index order in fp64: the error of an output is a few
+ * 2^-24 of the sum of its terms' magnitudes, and the result is bitwise the same on every call and
+ * stream (no atomics).
+ * Supported: 1 <= D <= HMM355_GMM_STATS_MAX_DIM (else HMM355_E_SHAPE), 1 <= C <= 256 and
+ * 1 <= S*C <= 65536 (else HMM355_E_STATES), T >= 1 and B*T < 2^31 (else HMM355_E_SHAPE).
+ * HMM355_E_ARG for a negative size, a null x / weight / means / log_vars / workspace, or
+ * mix_lse == 0 with C > 1; HMM355_E_WORKSPACE for a short workspace; B == 0 is a no-op.  Every
+ * check comes before any launch; the size query returns 0 for an unsupported shape.
+ * workspace >= hmm355_gmm_stats_workspace_bytes(B,T,D,S,C): three fp64 (D,S*C) parameter tables
+ * and one (2D+1, S*C) fp32 partial sum per frame span (at most 512 spans); nothing proportional to
+ * frames * S*C.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_GMM_STATS_MAX_DIM 1024
+size_t hmm355_gmm_stats_workspace_bytes(int B, int T, int D, int S, int C);
+int hmm355_gmm_stats_f32(const float* x, const float* weight, const float* means, const float* log_vars,
+                         const float* log_w /* or NULL */, const int* lengths /* (B) or NULL */, int B, int T,
+                         int D, int S, int C, int mix_lse, float* occ /* (S,C) or NULL */,
+                         float* sx /* (S,C,D) or NULL */, float* sxx /* (S,C,D) or NULL */, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * HSMM segment Viterbi.  Replaces HSMMLayer.viterbi_decode_hsmm / _viterbi_decode_single
  * (hsmm.py:208-354), reproducing its candidate order (s' outer, d' inner, strict >), its

@@ -44,3 +44,8 @@ __all__ += ["DurationConstrainedHMM", "compute_state_durations", "create_duratio
 from .ops import posterior_sample
 
 __all__ += ["posterior_sample"]
+
+from . import em
+from .em import EStats, e_step, gaussian_m_step, transition_m_step
+
+__all__ += ["em", "EStats", "e_step", "transition_m_step", "gaussian_m_step"]

@@ -46,6 +46,7 @@ DURFORCED_GRAD = 0x4  # HMM355_DURFORCED_GRAD: the size query's flag for hmm355_
 DURFORCED_MAX_POSITIONS = 1024  # HMM355_DURFORCED_MAX_POSITIONS
 DURFORCED_MAX_DURATION = 128  # HMM355_DURFORCED_MAX_DURATION
 DURFORCED_MAX_CELLS = 16384  # HMM355_DURFORCED_MAX_CELLS: positions times max_duration
+GMM_STATS_MAX_DIM = 1024  # HMM355_GMM_STATS_MAX_DIM
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -74,6 +75,7 @@ EXPORTS = (
     "hmm355_durforced_workspace_bytes", "hmm355_durforced_f32", "hmm355_durforced_grad_f32",
     "hmm355_viterbi_ragged_workspace_bytes", "hmm355_viterbi_ragged_f32", "hmm355_forward_backward_ragged_f32",
     "hmm355_ffbs_workspace_bytes", "hmm355_ffbs_f32",
+    "hmm355_gmm_stats_workspace_bytes", "hmm355_gmm_stats_f32",
 )
 
 _lib = None
@@ -192,6 +194,9 @@ def lib():
     L.hmm355_forward_backward_ragged_f32.restype = I
     L.hmm355_ffbs_workspace_bytes.argtypes, L.hmm355_ffbs_workspace_bytes.restype = [I], S
     L.hmm355_ffbs_f32.argtypes, L.hmm355_ffbs_f32.restype = [P, I, P, P, P, I, I, I, I, P, P, S, P], I
+    L.hmm355_gmm_stats_workspace_bytes.argtypes, L.hmm355_gmm_stats_workspace_bytes.restype = [I, I, I, I, I], S
+    L.hmm355_gmm_stats_f32.argtypes = [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, S, P]
+    L.hmm355_gmm_stats_f32.restype = I
     _lib = L
     return L
 

@@ -225,6 +225,25 @@ class HMMPyTorch(HMM):
             out = out.squeeze(1)
         return out.squeeze(0) if squeeze else out
 
+    def reestimate(self, observations: torch.Tensor, lengths=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Extension: one Baum-Welch re-estimation of the chain for given emissions (em.e_step and
+        em.transition_m_step): (P_new (K,K), p0_new (K), loglik (B,)) with loglik the exact
+        log-likelihood under the current parameters.  The emissions are the class's own,
+        log(observations + 1e-8), with log_P and log_p0 as the recursions use them.  The object is
+        not modified; a state that is never occupied keeps its row of P.  At most 256 states."""
+        from . import em
+        obs, _ = self._as_batch(observations)
+        if obs.dim() != 3 or obs.shape[-1] != self.K:
+            raise ValueError(f"observations must be (B, T, {self.K}); got {tuple(observations.shape)}")
+        from . import _native as nat
+        nat.require_gpu(obs)
+        log_P, log_p0, plan = self._device_params(obs.device)
+        with torch.no_grad():
+            es = em.e_step(torch.log(obs.detach() + 1e-8), log_P.detach(), log_p0.detach(), lengths, plan)
+            P, p0 = em.transition_m_step(es.xi, es.gamma0, es.n_seq, self.P.detach().to(obs.device),
+                                         self.p0.detach().to(obs.device))
+        return P, p0, es.loglik
+
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """Sample (states, one-hot observations) — reference hmm.py:213-245 (not on the hot
         path; plain torch sampling on the parameters' device)."""

@@ -242,6 +242,78 @@ class GaussianHMMLayer(nn.Module):
             probs = self._observation_probs(x, lengths)
         return self.hmm_layer.sample_alignment(probs, num_samples, lengths, generator)
 
+    # -- Baum-Welch (em.py) ----------------------------------------------------------------
+    _EM_UPDATES = ("transitions", "initial", "means", "variances")
+
+    def _em_model(self):
+        """(log_P, log_p0) of the E-step: log_softmax of the logits, or log of the fixed
+        transition matrix with -inf at its zeros."""
+        from . import em
+        hl = self.hmm_layer
+        if hl.log_transition_logits is not None:
+            log_P = F.log_softmax(hl.log_transition_logits, dim=1)
+        else:
+            log_P = em.log_of(hl.transition_matrix)
+        return log_P, F.log_softmax(hl.log_initial_logits, dim=0)
+
+    def _em_iteration(self, batches, update, var_floor):
+        """One EM iteration over `batches` ([(x, lengths)]); (total log-likelihood under the
+        parameters before the update, frames)."""
+        from . import em
+        if self.covariance_type == "full":
+            raise NotImplementedError("em_step covers covariance_type 'diag' and 'spherical', not 'full'")
+        em.check_update(update, self._EM_UPDATES, "GaussianHMMLayer.em_step")
+        S, D = self.num_states, self.feature_dim
+        hl = self.hmm_layer
+        with torch.no_grad():
+            mu = self.means.detach().unsqueeze(1)
+            lv = _gaussian_component_params(self.log_scales.detach(), self.covariance_type, D).contiguous()
+            log_w = torch.zeros(S, 1, device=mu.device)
+            log_P, log_p0 = self._em_model()
+            score = lambda x: ops.gmm_diag_logprob(x, mu, lv, log_w, 0)
+            stats = lambda x, gamma, lens: ops.gmm_stats(x, gamma, mu, lv, log_w, 0, lens)
+            want = "means" in update or "variances" in update
+            es, sums, frames = em.accumulate(batches, D, S, score, stats, log_P, log_p0, want_stats=want)
+            if "transitions" in update or "initial" in update:
+                P, p0 = em.transition_m_step(es.xi, es.gamma0, es.n_seq, torch.exp(log_P), torch.exp(log_p0))
+                if "transitions" in update:
+                    if hl.log_transition_logits is not None:
+                        hl.log_transition_logits.copy_(torch.log(P.clamp(min=1e-30)))
+                    else:
+                        hl.transition_matrix.copy_(P)
+                if "initial" in update:
+                    hl.log_initial_logits.copy_(torch.log(p0.clamp(min=1e-30)))
+            if want:
+                old_lv = (2 * self.log_scales.detach()).reshape(S, 1, -1) if self.covariance_type == "diag" else \
+                    (2 * self.log_scales.detach()).reshape(S, 1)
+                new_mu, new_lv, _ = em.gaussian_m_step(*sums, mu, self.covariance_type, var_floor, log_vars=old_lv)
+                if "means" in update:
+                    self.means.copy_(new_mu.squeeze(1))
+                if "variances" in update:
+                    self.log_scales.copy_(0.5 * new_lv.reshape(self.log_scales.shape))
+        return float(es.loglik.sum(dtype=torch.float64)), frames
+
+    def em_step(self, observations: torch.Tensor, lengths=None, *,
+                update=("transitions", "initial", "means", "variances"), var_floor: float = 1e-4) -> float:
+        """One Baum-Welch iteration on observations (B,T,D) (lengths: one length per sequence of a
+        padded batch, or None); returns the total log-likelihood under the parameters BEFORE the
+        update.  E-step model: the scorer's Gaussian log-densities as log-emissions, log_P =
+        log_softmax(log_transition_logits) (or the log of the fixed transition_matrix, -inf at its
+        zeros), log_p0 = log_softmax(log_initial_logits).  The M-step writes, in place and for the
+        names in `update`: log_transition_logits = log(clamp(P', 1e-30)) (or the transition_matrix
+        buffer), log_initial_logits likewise, means, and log_scales = log(var') / 2 with var' floored
+        at var_floor.  covariance_type 'diag' and 'spherical'; 'full' raises NotImplementedError."""
+        from . import em
+        return self._em_iteration(em.as_batches(observations, lengths), tuple(update), var_floor)[0]
+
+    def fit(self, observations, lengths=None, n_iter: int = 10, tol: float = 1e-4):
+        """Up to n_iter EM iterations (em_step); returns the total log-likelihood before each
+        iteration and stops once the gain per frame drops below tol.  observations may be a list of
+        (x, lengths) pairs: their statistics are summed before each M-step."""
+        from . import em
+        batches = em.as_batches(observations, lengths)
+        return em.run_fit(lambda: self._em_iteration(batches, self._EM_UPDATES, 1e-4), n_iter, tol)
+
     def extra_repr(self) -> str:
         return (f"num_states={self.num_states}, feature_dim={self.feature_dim}, "
                 f"covariance_type={self.covariance_type}")

@@ -269,6 +269,100 @@ class MixtureGaussianHMMLayer(nn.Module):
                                              generator=generator)
         return states
 
+    # -- Baum-Welch (em.py) ----------------------------------------------------------------
+    _EM_UPDATES = ("transitions", "means", "variances", "weights")
+
+    def _em_model(self, device):
+        """(log_P, log_p0, log_w) of the E-step and of log_likelihood: log_softmax of the
+        transition logits (or the log of the fixed transition_matrix, -inf at its zeros), the
+        uniform start vector of the decode, and the decode's log mixture weights."""
+        from . import em
+        if self.learnable_transitions:
+            log_P = F.log_softmax(self.transition_logits, dim=-1)
+        else:
+            log_P = em.log_of(self.transition_matrix)
+        log_p0 = -(torch.zeros(self.num_states, device=device) + math.log(self.num_states))
+        return log_P, log_p0, self._safe_log(F.softmax(self.mixture_weights_logits, dim=-1))
+
+    def _em_check(self):
+        if self.covariance_type == "full":
+            raise NotImplementedError("EM and log_likelihood cover covariance_type 'diag', 'tied' and 'spherical', "
+                                      "not 'full'")
+
+    def _em_iteration(self, batches, update, var_floor):
+        """One EM iteration over `batches` ([(x, lengths)]); (total log-likelihood under the
+        parameters before the update, frames)."""
+        from . import em
+        self._em_check()
+        if "initial" in update:
+            raise ValueError("MixtureGaussianHMMLayer has no initial distribution to update: its start vector is "
+                             "the fixed uniform one of its decode")
+        em.check_update(update, self._EM_UPDATES, "MixtureGaussianHMMLayer.em_step")
+        S, C, D = self.num_states, self.num_components, self.feature_dim
+        with torch.no_grad():
+            mu = self.means.detach()
+            lv = self._component_log_vars().detach().contiguous()
+            log_P, log_p0, log_w = self._em_model(mu.device)
+            score = lambda x: ops.gmm_diag_logprob(x, mu, lv, log_w, 1)
+            stats = lambda x, gamma, lens: ops.gmm_stats(x, gamma, mu, lv, log_w, 1, lens)
+            want = any(u in update for u in ("means", "variances", "weights"))
+            es, sums, frames = em.accumulate(batches, D, S, score, stats, log_P, log_p0, want_stats=want)
+            if "transitions" in update:
+                P, _ = em.transition_m_step(es.xi, es.gamma0, es.n_seq, torch.exp(log_P), torch.exp(log_p0))
+                if self.learnable_transitions:
+                    self.transition_logits.copy_(torch.log(P.clamp(min=1e-30)))
+                else:
+                    self.transition_matrix.copy_(P)
+            if want:
+                new_mu, new_lv, new_w = em.gaussian_m_step(*sums, mu, self.covariance_type, var_floor,
+                                                           log_vars=self.log_vars.detach(), weights=torch.exp(log_w))
+                if "means" in update:
+                    self.means.copy_(new_mu)
+                if "variances" in update:
+                    self.log_vars.copy_(new_lv.reshape(self.log_vars.shape))
+                if "weights" in update:
+                    self.mixture_weights_logits.copy_(torch.log(new_w.clamp(min=1e-30)))
+        self.refresh_tables()
+        return float(es.loglik.sum(dtype=torch.float64)), frames
+
+    def em_step(self, observations: torch.Tensor, lengths=None, *,
+                update=("transitions", "means", "variances", "weights"), var_floor: float = 1e-4) -> float:
+        """One Baum-Welch iteration on observations (B,T,D) (lengths: one length per sequence of a
+        padded batch, or None); returns the total log-likelihood under the parameters BEFORE the
+        update.  E-step model: the mixture log-densities of the scorer as log-emissions, log_P =
+        log_softmax(transition_logits) (or the log of the fixed transition_matrix, -inf at its
+        zeros) and the decode's uniform start vector, which is why `update` never holds "initial".
+        The M-step writes, in place and for the names in `update`: transition_logits =
+        log(clamp(P', 1e-30)) (or the transition_matrix buffer), means, log_vars (in the covariance
+        type's shape, var' floored at var_floor) and mixture_weights_logits = log(clamp(w', 1e-30)).
+        covariance_type 'diag', 'tied' and 'spherical'; 'full' raises NotImplementedError."""
+        from . import em
+        return self._em_iteration(em.as_batches(observations, lengths), tuple(update), var_floor)[0]
+
+    def fit(self, observations, lengths=None, n_iter: int = 10, tol: float = 1e-4):
+        """Up to n_iter EM iterations (em_step); returns the total log-likelihood before each
+        iteration and stops once the gain per frame drops below tol.  observations may be a list of
+        (x, lengths) pairs: their statistics are summed before each M-step."""
+        from . import em
+        batches = em.as_batches(observations, lengths)
+        return em.run_fit(lambda: self._em_iteration(batches, self._EM_UPDATES, 1e-4), n_iter, tol)
+
+    def log_likelihood(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
+        """(B,) exact log-likelihood log p(x_b) of each sequence under the model em_step
+        re-estimates (mixture emissions, log_softmax transitions, uniform start).  No gradients."""
+        from . import em
+        self._em_check()
+        x, lens, _ = em.check_batch(observations, lengths, self.feature_dim, self.num_states)
+        with torch.no_grad():
+            log_P, log_p0, log_w = self._em_model(x.device)
+            if lens is not None:
+                valid = valid_frames(lens, x.shape[1], x.device)
+                x = torch.where(valid[..., None], x, torch.zeros_like(x))
+            lp = ops.gmm_diag_logprob(x, self.means.detach(), self._component_log_vars().detach(), log_w, 1)
+            if lens is not None:
+                return ops.forward_backward_ragged(lp, log_P, log_p0, ops.OBS_LOG, lens, 0)[3]
+            return ops.forward_backward(lp, log_P, log_p0, ops.OBS_LOG, 0)[3]
+
     def get_model_info(self) -> dict:
         total = sum(p.numel() for p in self.parameters())
         trainable = sum(p.numel() for p in self.parameters() if p.requires_grad)

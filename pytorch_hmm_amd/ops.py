@@ -41,6 +41,7 @@ shape-only fake implementations; their only real implementation is the HIP libra
                                   input_lengths, state_lengths, dur_lp, want_gamma=, want_grad=, want_dur=)
       -> (gamma, grad_log_probs, grad_dur_lp)
   torch.ops.hmm355.ffbs(fwd, log_P, uniforms, lengths) -> states (B,K,T)     posterior path samples
+  torch.ops.hmm355.gmm_stats(x, weight, means, log_vars, log_w, mix_lse, lengths) -> (occ, sx, sxx)
 """
 from typing import Optional, Tuple
 
@@ -428,6 +429,61 @@ def gmm_diag_logprob(x: Tensor, means: Tensor, log_vars: Tensor, log_w: Tensor, 
 @gmm_diag_logprob.register_fake
 def _(x, means, log_vars, log_w, mix_lse):
     return x.new_empty((x.shape[0], x.shape[1], means.shape[0]))
+
+
+@torch.library.custom_op("hmm355::gmm_stats", mutates_args=())
+def gmm_stats(x: Tensor, weight: Tensor, means: Tensor, log_vars: Tensor, log_w: Tensor, mix_lse: int,
+              lengths: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Occupancy-weighted sufficient statistics of the diagonal Gaussian (mixture) emissions
+    (hmm355_gmm_stats_f32, csrc/emstats.hip; spelled out in include/hmm355.h): with r the component
+    responsibilities of the scorer's model and w = weight * r,
+        occ (S,C) = sum w,  sx (S,C,D) = sum w (x - mu),  sxx (S,C,D) = sum w (x - mu)^2
+    over the frames t < lengths[b] of every sequence.  x (B,T,D), weight (B,T,S) of any sign (the
+    E-step passes the state posteriors), means / log_vars (S,C,D), log_w (S,C), mix_lse as
+    gmm_diag_logprob (0 needs C == 1: r = 1), lengths (B) or None.  Frames past a length are never
+    read.  Bitwise reproducible; no (frames, S*C) temporary."""
+    if x.dim() != 3 or weight.dim() != 3 or means.dim() != 3:
+        raise ValueError(f"x, weight and means must be (B,T,D), (B,T,S) and (S,C,D); got {tuple(x.shape)}, "
+                         f"{tuple(weight.shape)}, {tuple(means.shape)}")
+    B, T, D = x.shape
+    S, C, D2 = means.shape
+    if D2 != D:
+        raise ValueError(f"feature dim mismatch: x has {D}, means have {D2}")
+    if tuple(weight.shape) != (B, T, S):
+        raise ValueError(f"weight must be (B, T, S) = ({B}, {T}, {S}); got {tuple(weight.shape)}")
+    if tuple(log_vars.shape) != (S, C, D) or tuple(log_w.shape) != (S, C):
+        raise ValueError(f"log_vars must be ({S}, {C}, {D}) and log_w ({S}, {C}); got {tuple(log_vars.shape)}, "
+                         f"{tuple(log_w.shape)}")
+    if D > nat.GMM_STATS_MAX_DIM:
+        raise ValueError(f"gmm_stats supports at most {nat.GMM_STATS_MAX_DIM} feature dims; got {D}")
+    if C > 256 or S * C > 65536:
+        raise ValueError(f"gmm_stats supports at most 256 components per state and 65536 in all; got S={S}, C={C}")
+    if not mix_lse and C != 1:
+        raise ValueError(f"mix_lse == 0 needs one component per state; got C={C}")
+    host = None if lengths is None else ragged_lengths(lengths, B, T)
+    nat.require_gpu(x, weight, means, log_vars, log_w)
+    x, weight, means, log_vars, log_w = (_f32c(t.detach()) for t in (x, weight, means, log_vars, log_w))
+    dev = x.device
+    if B * T == 0:
+        return torch.zeros((S, C), device=dev), torch.zeros((S, C, D), device=dev), torch.zeros((S, C, D), device=dev)
+    occ = torch.empty((S, C), device=dev)
+    sx = torch.empty((S, C, D), device=dev)
+    sxx = torch.empty((S, C, D), device=dev)
+    lens = None if host is None else host.to(torch.int32).to(dev)
+    L = nat.lib()
+    ws = _workspace(L.hmm355_gmm_stats_workspace_bytes(B, T, D, S, C), dev)
+    with torch.cuda.device(dev):
+        nat.check(L.hmm355_gmm_stats_f32(
+            nat.ptr(x), nat.ptr(weight), nat.ptr(means), nat.ptr(log_vars), nat.ptr(log_w), nat.ptr(lens), B, T, D, S,
+            C, int(mix_lse), nat.ptr(occ), nat.ptr(sx), nat.ptr(sxx), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    return occ, sx, sxx
+
+
+@gmm_stats.register_fake
+def _(x, weight, means, log_vars, log_w, mix_lse, lengths=None):
+    S, C, D = means.shape
+    mk = lambda *shape: x.new_empty(shape, dtype=torch.float32)
+    return mk(S, C), mk(S, C, D), mk(S, C, D)
 
 
 # ------------------------------------------------------------------------------- HSMM
