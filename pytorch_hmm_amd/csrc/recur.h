@@ -34,11 +34,15 @@
 namespace hmm355 {
 
 enum RecKind : int { kFbAlpha = 0, kFbBeta = 1, kVit = 2 };
+typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned int))));  // (as fbpair.h)
 
 // diagnostic builds (HMM355_STAMP=1): per wave [gather, compute, write-wait, barrier, steps,
 // total cycles, memtime, memrealtime] summed over the steps (tools/stamps.py)
 constexpr int kStampWaves = 512 * 16;
 static __device__ unsigned long long g_rec_stamps[kStamp ? kStampWaves * 8 : 1];
+// HMM355_STAMP=2: also the staging helpers' block work by item and the psi waves (rec_band); these
+// stamps wait for the wave's LDS reads, so the chain's own figures are taken from a STAMP=1 build
+constexpr bool kStampItems = HMM355_STAMP > 1;
 
 template <int NP>
 struct RC {
@@ -1193,6 +1197,25 @@ __device__ __forceinline__ void rec_run_rb(const RecArgs& a, float* lds, int b) 
   lds_barrier();  // the last blocks' flush and the log-likelihood: the helpers
 }
 
+// Window term n of a register-window chain (band_chain, TW > 0: NB states per lane, offsets
+// TD0 + k): state j = n % NB, slot k = n / NB.  Its source NB*l + j + TD0 + k lies in another
+// lane -- one or two DPP lane shifts -- when this holds.
+constexpr bool win_term_shifted(int n, int NB, int TD0) { return (n % NB + TD0 + n / NB + 4 * NB) / NB != 4; }
+// its source as one number: register jj of the lane qq lanes on, NB * (qq + 4) + jj
+constexpr int win_term_src(int n, int NB, int TD0) { return n % NB + TD0 + n / NB + 4 * NB; }
+// the m-th distinct shifted source behind the first terms (k >= 1) of NWIN, as the first term
+// that reads it (two terms may read the same one: offsets 0 .. +2 at two states per lane);
+// m < 0: how many there are
+constexpr int win_shift_term(int m, int NB, int NWIN, int TD0) {
+  int c = 0;
+  for (int n = NB; n < NWIN; ++n) {
+    bool first = win_term_shifted(n, NB, TD0);
+    for (int p = NB; p < n; ++p) first = first && win_term_src(p, NB, TD0) != win_term_src(n, NB, TD0);
+    if (first && c++ == m) return n;
+  }
+  return c;
+}
+
 // The banded chain wave (wave 0 of rec_band; waves 0 and 1 of the forward-backward pair
 // kernel, fbpair.h): the whole recursion of one sequence in one wave, one lds_barrier per
 // 16-step block and one after the last row, matching the helpers' barriers.  `lds` is the
@@ -1209,8 +1232,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // ------------------------------------------------------------------ chain wave
   // Lane l holds the consecutive states s = NB*l + j (j < NB): a window offset of +-1 is
   // then another register of the same lane or ONE DPP lane shift (zero-filled at the wave
-  // edge, where the window weight is the neutral element), folded by the compiler into the
-  // add / fma that consumes it.  A wave issues one instruction per ~4 cycles, so the step is
+  // edge, where the window weight is the neutral element).  The compiler folds the shift into
+  // the instruction that consumes it where that is a VOP2 when the DPP combiner runs: Viterbi's
+  // add (v_add_f32_dpp) and the forward-backward window sum's first term, a product
+  // (v_mul_f32_dpp, see `term` below).  The sum's later terms are fmas then (VOP3, no DPP form;
+  // they become v_fmac only afterwards), so their shifts stay a v_mov_b32_dpp each (NP = 128
+  // listings).  A wave issues one instruction per ~4 cycles, so the step is
   // written for instruction count: 16-step blocks fully unrolled (no scalar address math),
   // the emission read one step ahead, the block's normalisers collected by v_writelane and
   // stored once per block.
@@ -1295,7 +1322,8 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // second reduction, the weighted sum, so its fmas stay behind.)
   // Units, in issue order (loads early, their consumers late):
   //   0 the window source's store | the window reads | beta, LDS mode: the row store |
-  //   the emission load | the window terms
+  //   the emission load | the window terms (beta, register windows: the first terms | the lane
+  //   shifts of the later terms | the later terms)
   // beta and Viterbi pin them inside the reduction (wave_red_fill).  alpha issues them ahead of
   // the plain reduction and leaves the placing to the compiler: pinned, its step measured slower
   // under every allocation tried.
@@ -1313,22 +1341,47 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     constexpr bool LW = TW == 0;                                     // LDS-window mode
     constexpr bool WFILL = !(KIND == kFbAlpha && !decltype(UA)::value);  // the window terms are fillers
     constexpr int NWIN = NB * WW;
+    // SPLIT (beta, register windows): a lane shift that no instruction can take in (below) is a
+    // unit of its own, ahead of the terms that read it, so a gap of the reduction can hold it alone
+    constexpr bool SPLIT = FILLED && FB && !LW;
+    constexpr int NSH = SPLIT ? win_shift_term(-1, NB, NWIN, TD0) : 0;
     constexpr int O_LD = 1, O_ST2 = O_LD + (LW ? NWIN : 0), O_EN = O_ST2 + (LW && KIND == kFbBeta ? 1 : 0);
-    constexpr int O_T = O_EN + 1, NU = O_T + (WFILL ? NWIN : 0);
+    constexpr int O_T = O_EN + 1, O_SH = O_T + (SPLIT ? NB : 0), NU = O_T + (WFILL ? NWIN + NSH : 0);
     float eo[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) eo[j] = en[j];
-    float acc[NB], src[NB], wl[NB][WW], tv[NB][WW];
+    float acc[NB], src[NB], wl[NB][WW], tv[NB][WW], sh[5 * NB];
     float cs = 0.f, scale = 1.f;
     const float* wsrc = KIND == kFbBeta ? ybuf + ((q - 1) & 1) * NP : row;
-    // window term n: (k, j) in the order of the plain loops (k ascending for every j)
+    // window term n: (k, j) in the order of the plain loops (k ascending for every j).
+    // FB, window sum from 0 (WFILL): term k = 0 is the product v * w, the later ones fmas into it.
+    // fma(v, w, +0) and v * w are the same bits unless the product is -0 (-0 + +0 = +0), and none
+    // is: chain values, the zero a lane shift fills in at the wave edge and window weights are all
+    // >= +0.  The multiply is VOP2, so a shifted first term is one v_mul_f32_dpp; the fma from 0
+    // is VOP3, which has no DPP form, and left its shift a v_mov_b32_dpp of its own.
     auto term = [&](int n) {
       const int j = LW ? n / WW : n % NB, k = LW ? n % WW : n / NB;
       float v;
       if constexpr (LW) v = wl[j][k];
-      else v = at(src, j, TD0 + k);
-      if (FB) acc[j] = fmaf(v, wv[j][k], acc[j]);
-      else tv[j][k] = v + wv[j][k];
+      else v = (SPLIT && k > 0 && win_term_shifted(n, NB, TD0)) ? sh[win_term_src(n, NB, TD0) - 2 * NB] : at(src, j, TD0 + k);
+      if (FB) {
+        if (WFILL && k == 0) {
+#pragma clang fp contract(off)
+          acc[j] = v * wv[j][k];
+        } else {
+          acc[j] = fmaf(v, wv[j][k], acc[j]);
+        }
+      } else {
+        tv[j][k] = v + wv[j][k];
+      }
+    };
+    // the m-th lane shift behind a first term: the fmac that reads it cannot take it in (the DPP
+    // combiner runs while it is still an fma), so it is a v_mov_b32_dpp wherever it stands
+    auto shift = [&](int m) {
+      const int n = win_shift_term(m, NB, NWIN, TD0);
+      float& s = sh[win_term_src(n, NB, TD0) - 2 * NB];  // (by source: a second reader takes it from here)
+      s = at(src, n % NB, TD0 + n / NB);
+      fill_pin(s);
     };
     auto unit = [&](auto I) {
       constexpr int i = decltype(I)::value;
@@ -1342,8 +1395,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         st(row + NB * l, y);
       } else if constexpr (i == O_EN) {
         if (!last_in_block) ld(enext, en);
+      } else if constexpr (i < O_SH) {
+        term(i - O_T);  // (SPLIT) the first terms
+      } else if constexpr (i < O_SH + NSH) {
+        shift(i - O_SH);
       } else {
-        term(i - O_T);
+        term(i - O_T - NSH);
       }
     };
     auto fill = [&](auto G) { static_for<fill_lo(decltype(G)::value, NU), fill_lo(decltype(G)::value + 1, NU)>(unit); };
@@ -1709,11 +1766,27 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
     // Straight-line block work (no branch around the staging or the loads: the tail stages
     // a block past the end as padding and re-loads the last block), so the waitcnt pass
     // keeps exact counts and never drains the in-flight prefetches or the flush stores.
-    // Viterbi with log leaders: `lp` holds the leaders' count as polled three blocks ago (read
-    // here, where the staging's wait has already retired that poll, so it never stalls the
-    // helper), and takes this block's poll.
+    // Viterbi with log leaders: `lp` holds the leaders' count word as polled three blocks ago, and
+    // takes this block's poll.  The word is kept as loaded and decoded (poll_count's rule) only
+    // where it is read, three blocks on, where the staging's wait has already retired that poll.
+    // Decoded where it was polled -- as it stood until round 9 -- the compiler waited for the
+    // load on the spot with vmcnt(0), which also drains the write-through flush and psi stores
+    // issued just before it: ~800 of a block's ~2900 cycles in every staging helper (stamps by
+    // item), and the chain waited for its helpers.  The poll is a
+    // buffer load (sc1, as the atomic load was) so that it needs no branch: without leaders the
+    // resource is empty and the load returns 0, which decodes to count 0.
+    const bool lpon = KIND == kVit && a.lready;
+    const __amdgpu_buffer_rsrc_t lp_rs =
+        make_rsrc(lpon ? static_cast<const void*>(a.lready + b * kPubStride) : static_cast<const void*>(a.obs), lpon ? 8 : 0);
+    auto lp_count = [&](const u32x2_t& v) -> int {
+      const unsigned lo = __builtin_amdgcn_readfirstlane(v[0]), hi32 = __builtin_amdgcn_readfirstlane(v[1]);
+      const unsigned c = lo ^ count_mix(a.token);
+      return (hi32 == a.token && c <= (unsigned)nblocks) ? (int)c : 0;
+    };
     // (diagnostic builds: a helper's cycles of block work and at the barrier)
-    unsigned long long hs_work = 0, hs_wait = 0;
+    // (hs_item: the work by item -- staging and loads | row flush | psi copy | polls and publish;
+    // the log-scale scan is in the whole but in no item)
+    unsigned long long hs_work = 0, hs_wait = 0, hs_item[4] = {0, 0, 0, 0};
     // Forward-backward end rows (post.h kEndBlocks): the rows of the chain's last two blocks are
     // still in the LDS ring when the chain ends, and were they left to the followers they would
     // be flushed, published, seen by a polling lane and read back before their posterior could
@@ -1783,7 +1856,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
         }
       }
     };
-    auto block_work = [&](int kb, float(&ernext)[HV][5], float(&erfree)[HV][5], int& lp, auto FULLC) {
+    auto block_work = [&](int kb, float(&ernext)[HV][5], float(&erfree)[HV][5], u32x2_t& lp, auto FULLC) {
       asm volatile("" ::: "memory");  // (block_work(kb - 1)'s stores stay ahead of this block's loads)
       unsigned long long hs0 = 0;
       if (kStamp) hs0 = stamp();
@@ -1793,9 +1866,10 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
       if (!(kAbl & abl::kBandNoFlush) && kb >= 2) lsv = rec_ls_scan<NP, KIND>(a, lds, b, kb - 2, base, w == 1);
       // Viterbi: the block's source -- the leaders' log rows when they are ready, else the raw
       // emissions (the staging takes the log)
-      const bool fromlog = KIND == kVit && a.lobuf && kload >= 4 && lp >= kload + 1;
+      const bool fromlog = KIND == kVit && a.lobuf && kload >= 4 && lp_count(lp) >= kload + 1;
       const float* src = fromlog ? a.lobuf : a.obs;
       const float vmode = (fromlog || a.obs_mode == HMM355_OBS_LOG) ? 1.f : 0.f;
+      unsigned long long hi0 = hs0, hi1 = 0;  // (diagnostic builds: the block work by item)
 #pragma unroll
       for (int h = 0; h < HV; ++h) {
         const int vw = vw_of(h);
@@ -1804,11 +1878,14 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
             rec_stage<NP, KIND, FUSE>(a, lds, kb + 1, vw, l, ernext[h]);
             rec_load<NP, KIND, decltype(FULLC)::value, FUSE>(a, b, kload, vw, l, erfree[h], src, vmode);
           }
+          if (kStampItems) { hi1 = stamp(); hs_item[0] += hi1 - hi0; hi0 = hi1; }
           if (!(kAbl & abl::kBandNoFlush) && kb >= 2) rec_flush<NP, KIND>(a, lds, b, kb - 2, l + 64 * vw, lsv);
+          if (kStampItems) { hi1 = stamp(); hs_item[1] += hi1 - hi0; hi0 = hi1; }
         }
       }
       psi_copy(kb - 3);
-      if (KIND == kVit && a.lready) lp = poll_count(a.lready + b * kPubStride, a.token, nblocks);
+      if (kStampItems) { hi1 = stamp(); hs_item[2] += hi1 - hi0; hi0 = hi1; }
+      if constexpr (KIND == kVit) lp = __builtin_amdgcn_raw_buffer_load_b64(lp_rs, 0, 0, kAuxSc1);
       // every fourth block (Viterbi: whole 64-step chunks of psi rows), after this block's loads
       // (so the stores it signals are never waited for sooner than three blocks on); with end
       // rows every block of the chain's last kLateBlocks, so that what the followers still have
@@ -1819,15 +1896,23 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
         if (cnt > 0 && ((cnt & 3) == 0 || late)) publish_count(pubp, cnt, a.token);
       }
       unsigned long long hs1 = 0;
-      if (kStamp) { hs1 = stamp(); hs_work += hs1 - hs0; }
+      if (kStamp) { hs1 = stamp(); hs_work += hs1 - hs0; hs_item[3] += kStampItems ? hs1 - hi0 : 0; }
       if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();
       if (kStamp) hs_wait += stamp() - hs1;
     };
     if constexpr (FUSE) {
       if (psiw) {  // psi-only waves: one compact loop, same barrier count as the helpers
         for (int kb = 0; kb < nblocks; ++kb) {
+          unsigned long long ps0 = 0, ps1 = 0;
+          if (kStampItems) ps0 = stamp();
           psi_rows(kb - 2);
+          if (kStampItems) { ps1 = stamp(); hs_work += ps1 - ps0; }
           if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();
+          if (kStampItems) hs_wait += stamp() - ps1;
+        }
+        if (kStampItems && l == 0) {
+          unsigned long long* o8 = g_rec_stamps + (((size_t)blockIdx.x * 16 + w) % kStampWaves) * 8;
+          o8[0] = hs_work; o8[1] = hs_wait; o8[4] = (unsigned long long)nblocks;
         }
         lds_barrier();  // the chain's last row
         psi_rows(nblocks - 2);
@@ -1836,7 +1921,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
         return;
       }
     }
-    int lp0 = 0, lp1 = 0, lp2 = 0;  // the leaders' polls (block kb's is read at kb + 3)
+    u32x2_t lp0 = {0u, 0u}, lp1 = lp0, lp2 = lp0;  // the leaders' polls (block kb's is read at kb + 3)
     auto helper_loop = [&](auto FULLC) {
       for (int kb = 0; kb < nblocks; kb += 3) {
         block_work(kb, er1, er0, lp0, FULLC);
@@ -1852,6 +1937,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
     if (kStamp && l == 0 && stager) {
       unsigned long long* o8 = g_rec_stamps + (((size_t)blockIdx.x * 16 + w) % kStampWaves) * 8;
       o8[0] = hs_work; o8[1] = hs_wait; o8[4] = (unsigned long long)nblocks;
+      o8[3] = hs_item[0]; o8[5] = hs_item[1]; o8[6] = hs_item[2]; o8[7] = hs_item[3];
     }
     if (endson) end_load();  // (the chain runs its last block: the helpers only wait for it)
     lds_barrier();  // the chain's last row and c_{T-1}

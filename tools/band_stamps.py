@@ -1,7 +1,7 @@
 """Diagnostic: cycles and shader clock of the banded chain waves (HMM355_STAMP=1 build,
 recur.h band_chain), each op alone and both ops side by side on two streams.
-Build here:  python tools/band_stamps.py build        Run on the GPU box: python tools/band_stamps.py [f]
-(f: the work beside the chains on).  Per chain: cycles per step, cycles per step at the block
+Build here:  python tools/band_stamps.py build [items]     Run on the GPU box: python tools/band_stamps.py [f]
+(f: the work beside the chains on; items: also the staging helpers' work by item and the psi waves).  Per chain: cycles per step, cycles per step at the block
 barriers (waiting for the helpers), and the clock (s_memtime cycles / s_memrealtime at 100 MHz)."""
 import ctypes
 import os
@@ -9,10 +9,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.environ.get("STAMP_LIB", os.path.join(HERE, "ablate_libs", "libhmm355_stamp.so"))
-if sys.argv[1:] == ["build"]:
+if sys.argv[1:2] == ["build"]:
+    # `build items`: HMM355_STAMP=2, which also stamps the staging helpers' block work by item and
+    # the psi waves; those stamps slow the helpers, so the chains' figures come from a plain build
     sys.path.insert(0, os.path.dirname(HERE))
     from pytorch_hmm_amd import build_native as bn
-    print(bn.build(force=True, defines=["HMM355_STAMP=1"], out=LIB, sources=bn.RECURSION_SOURCES))
+    level = 2 if sys.argv[2:] == ["items"] else 1
+    print(bn.build(force=True, defines=[f"HMM355_STAMP={level}"], out=LIB, sources=bn.RECURSION_SOURCES))
     sys.exit(0)
 import numpy as np
 import torch
@@ -64,8 +67,9 @@ def chain_exit(name, tag, nblk, t0):
         print(f"  {name:10s} chain workgroups' exit {float(np.median(x - t0)) / 100:6.1f} (last {(x - t0).max() / 100:6.1f})", flush=True)
 
 
-def helpers(name, tag, nblk, waves):
-    """cycles per block of the staging helpers' work and their wait at the block barrier"""
+def helpers(name, tag, nblk, waves, psi=()):
+    """cycles per block of the staging helpers' work, whole and by item, and their wait at the
+    block barrier; the same two for the psi waves of the fused Viterbi chain"""
     sym = getattr(L, f"hmm355_debug_stamps_{tag}")
     sym.argtypes = [ctypes.c_void_p, ctypes.c_int]
     n = 512 * 16 * 8
@@ -74,7 +78,15 @@ def helpers(name, tag, nblk, waves):
     a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, NW, 8)[:nblk].astype(np.float64)
     for w in waves:
         nb = np.maximum(a[:, w, 4], 1)
-        print(f"  {name:10s} helper wave {w:2d}: work/block {np.mean(a[:, w, 0] / nb):7.0f}  wait/block {np.mean(a[:, w, 1] / nb):7.0f}")
+        item = [np.mean(a[:, w, k] / nb) for k in (3, 5, 6, 7)]  # (0 unless the build stamps them: `build items`)
+        print(f"  {name:10s} helper wave {w:2d}: work/block {np.mean(a[:, w, 0] / nb):7.0f}  wait/block {np.mean(a[:, w, 1] / nb):7.0f}"
+              + (f"  stage+load {item[0]:6.0f}  flush {item[1]:6.0f}  psi copy {item[2]:6.0f}  poll+publish {item[3]:6.0f}"
+                 if max(item) > 0 else ""))
+    for w in psi:
+        if a[:, w, 4].max() <= 0:
+            continue  # (not stamped by this build)
+        nb = np.maximum(a[:, w, 4], 1)
+        print(f"  {name:10s} psi wave    {w:2d}: work/block {np.mean(a[:, w, 0] / nb):7.0f}  wait/block {np.mean(a[:, w, 1] / nb):7.0f}")
 
 
 def read(tag, nblk):
@@ -123,7 +135,7 @@ for mode in ("fb", "vit", "both"):
         chain_exit("fb", "fb", 2 * B, late[:, 0].min())
     if mode in ("vit", "both"):
         show("viterbi", read("vit", B))
-        helpers("vit", "vit", B, (1, 2, 3, 9, 10, 11))
+        helpers("vit", "vit", B, (1, 2, 3, 9, 10, 11), (5, 6, 7, 13, 14, 15))
         r = raw("vit", 2 * B)
         timeline("vit", r[:B], r[B:] if fl else None, 4)
         chain_exit("vit", "vit", B, r[:B, 0].min())
