@@ -526,55 +526,69 @@ class GmmLogProb(torch.autograd.Function):
     mixture_gaussian.py:141-155; r = 1 when mix_lse == 0):
         d/d means   = r g (x - mu) / var          d/d log_vars = r g ((x - mu)^2 / var - 1) / 2
         d/d x       = -sum_{s,c} r g (x - mu) / var                d/d log_w = r g
-    expanded into GEMMs over the frames (hipBLASLt through torch.matmul), T-chunked."""
+    expanded into GEMMs over the frames (torch.matmul), T-chunked.
+
+    Precision.  The expansion x^2 iv - 2 x (mu iv) + sum mu^2 iv and the moments
+    gx2 - 2 mu gx1 + mu^2 gsum cancel: with features that are not centred (x, mu ~ off, spread xs)
+    the terms are (off / xs)^2 times the result, and in fp32 that lost 2-3 digits against fp32
+    autograd of the direct (x - mu)^2 / var form (tests/test_gpu_gmm.py: 41 to 4490 x its error
+    on the cases with off != 0).  The component scores, the GEMMs and the moment algebra
+    therefore run in float64, like the forward scorer's quadratic form (csrc/gmm.hip); the
+    gradients are rounded to the inputs' dtypes once, at the end.  Each product pair shares one
+    GEMM ([x^2, x] against stacked tables) and the responsibilities are one fused softmax: the
+    passes over the (frames, S*C) temporaries, not the fp64 GEMMs, set the time."""
+
+    # bytes of one (frames, S*C) temporary of the backward's T-chunks
+    _CHUNK_BYTES = 16 << 20
 
     @staticmethod
     def forward(ctx, x, means, log_vars, log_w, mix_lse):
         from . import ops
         lp = ops.gmm_diag_logprob(x.detach(), means.detach(), log_vars.detach(), log_w.detach(), mix_lse)
-        ctx.save_for_backward(x, means, log_vars, log_w, lp)
+        ctx.save_for_backward(x, means, log_vars, log_w)
         ctx.mix_lse = mix_lse
         return lp
 
     @staticmethod
     def backward(ctx, g):
-        x, means, log_vars, log_w, lp = ctx.saved_tensors
+        x, means, log_vars, log_w = ctx.saved_tensors
         B, T, D = x.shape
         S, C, _ = means.shape
-        mu = means.detach().float().reshape(S * C, D)
-        lv = log_vars.detach().float().reshape(S * C, D)
+        f64 = torch.float64
+        mu = means.detach().to(f64).reshape(S * C, D)
+        lv = log_vars.detach().to(f64).reshape(S * C, D)
         iv = torch.exp(-lv)                                   # 1 / var
-        cst = lv.sum(-1) + D * math.log(2 * math.pi)          # (SC)
-        lw = log_w.detach().float().reshape(S * C)
-        q2 = (mu * mu * iv).sum(-1)                           # sum mu^2 / var
-        gm = torch.zeros_like(mu)      # sum gc (x - mu) / var  pieces
-        gx2 = torch.zeros_like(mu)     # sum gc x^2
-        gx1 = torch.zeros_like(mu)     # sum gc x
-        gsum = torch.zeros(S * C, device=x.device)
-        grad_x = torch.empty_like(x, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        step = max(1, (1 << 22) // max(1, B * S * C))       # frames-of-T per chunk (bounded temp)
-        xf = x.detach().float()
+        miv = mu * iv
+        if ctx.mix_lse:
+            # comp = [x^2, x] @ wcat + bias, one GEMM: -0.5 (x^2 iv - 2 x mu iv + sum mu^2 iv + K) + log_w
+            lw = log_w.detach().to(f64)
+            # a state whose components all have log_w = -inf: the reference's m = -inf -> 0 and
+            # clamp(min=1e-8) leave it a zero slope; its log_w is cleared so the softmax stays finite
+            alive = ~torch.isneginf(lw).all(-1)               # (S)
+            lw = torch.where(alive[:, None], lw, torch.zeros_like(lw)).reshape(S * C)
+            bias = lw - 0.5 * ((mu * miv).sum(-1) + lv.sum(-1) + D * math.log(2 * math.pi))
+            wcat = torch.cat([-0.5 * iv, miv], 1).t()         # (2D, SC)
+        xcat = torch.cat([miv, iv], 1)                        # (SC, 2D): grad_x's two products
+        gxx = torch.zeros(S * C, 2 * D, device=x.device, dtype=f64)    # sum gc [x^2, x]
+        gsum = torch.zeros(S * C, device=x.device, dtype=f64)
+        grad_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        # frames-of-T per chunk: the (frames, S*C) float64 temporaries stay at _CHUNK_BYTES each
+        step = max(1, GmmLogProb._CHUNK_BYTES // (mu.element_size() * max(1, B * S * C)))
         for t0 in range(0, T, step):
-            xc = xf[:, t0:t0 + step].reshape(-1, D)           # (F, D)
-            gl = g[:, t0:t0 + step].reshape(-1, S).float()    # (F, S)
-            maha = (xc * xc) @ iv.t() - 2.0 * (xc @ (mu * iv).t()) + q2   # (F, SC)
-            comp = -0.5 * (maha + cst) + lw
+            xc = x.detach()[:, t0:t0 + step].reshape(-1, D).to(f64)     # (F, D)
+            gl = g[:, t0:t0 + step].reshape(-1, S).to(f64)              # (F, S)
+            xx = torch.cat([xc * xc, xc], 1)                            # (F, 2D)
             if ctx.mix_lse:
-                comp3 = comp.view(-1, S, C)
-                m = comp3.max(-1, keepdim=True)[0]
-                m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-                ex = torch.exp(comp3 - m)
-                se = ex.sum(-1, keepdim=True)
-                r = torch.where(se > 1e-8, ex / se, torch.zeros_like(ex))   # clamp(min=1e-8) has 0 slope below
-                gc = (r * gl.unsqueeze(-1)).reshape(-1, S * C)
+                r = torch.softmax(torch.addmm(bias, xx, wcat).view(-1, S, C), -1)
+                gc = r.mul_((gl * alive).unsqueeze(-1)).view(-1, S * C)
             else:
-                gc = gl.reshape(-1, S * C)
+                gc = gl
             gsum += gc.sum(0)
-            gx1 += gc.t() @ xc
-            gx2 += gc.t() @ (xc * xc)
+            gxx += gc.t() @ xx
             if grad_x is not None:
-                gxx = -(xc * (gc @ iv) - gc @ (mu * iv))
-                grad_x[:, t0:t0 + step] = gxx.view(B, -1, D)
+                o = gc @ xcat
+                grad_x[:, t0:t0 + step] = torch.addcmul(o[:, :D], xc, o[:, D:], value=-1.0).view(B, -1, D)
+        gx2, gx1 = gxx[:, :D], gxx[:, D:]
         grad_means = (gx1 - mu * gsum[:, None]) * iv
         grad_lv = 0.5 * ((gx2 - 2 * mu * gx1 + mu * mu * gsum[:, None]) * iv - gsum[:, None])
         return (grad_x, grad_means.view(S, C, D).to(means.dtype), grad_lv.view(S, C, D).to(log_vars.dtype),
