@@ -30,6 +30,7 @@ import math
 import torch
 
 from . import _native as nat
+from . import ops
 
 
 def needs_grad(*tensors) -> bool:
@@ -61,6 +62,14 @@ def _require_narrow(N, what):
             "forward-backward runs without autograd support (call it under torch.no_grad() / on detached inputs)")
 
 
+def _fb_outputs(dev, B, T, N, mask):
+    """((posterior, forward, backward, loglik, lik_ref), their five pointers for the entry point): the
+    ops' forward-backward outputs (ops._fb_outputs), with None for one the mask leaves out."""
+    outs = ops._fb_outputs(ops._on(dev), B, T, N, mask)
+    wanted = (o if mask & bit else None for o, bit in zip(outs, (nat.FB_POSTERIOR, nat.FB_FORWARD, nat.FB_BACKWARD)))
+    return (*wanted, outs[3], outs[4]), ops._fb_ptrs(outs, mask)
+
+
 def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_mask=None, plan=None, lengths=None):
     """One hmm355_forward_backward_plan_f32 call; returns (posterior|None, loglik, lik_ref, U, V,
     LA, LB), or with `out_mask` ((posterior, forward, backward) per the mask, loglik, lik_ref, U,
@@ -71,26 +80,20 @@ def _run_fb(obs, log_P, log_p0, obs_mode, log_beta_T=None, posterior=False, out_
     NP = _pad(N)
     dev = obs.device
     L = nat.lib()
-    ws = torch.empty(L.hmm355_fb_workspace_bytes(B, T, N), dtype=torch.uint8, device=dev)
     mask = out_mask if out_mask is not None else (nat.FB_POSTERIOR if posterior else 0)
-    mk = lambda bit: torch.empty(B, T, N, device=dev) if mask & bit else None
-    post, fwd, bwd = mk(nat.FB_POSTERIOR), mk(nat.FB_FORWARD), mk(nat.FB_BACKWARD)
-    loglik = torch.empty(B, device=dev)
-    lik_ref = torch.empty(B, device=dev)
-    with torch.cuda.device(dev):
-        if lengths is not None:
-            lens = lengths.to(torch.int32).to(dev)
-            nat.check(L.hmm355_forward_backward_ragged_f32(
-                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(log_beta_T), nat.ptr(lens), B, T, N,
-                mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
-                nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-        else:
-            nat.check(L.hmm355_forward_backward_plan_f32(
-                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(plan), nat.ptr(log_beta_T), B, T, N,
-                mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
-                nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    (post, fwd, bwd, loglik, lik_ref), ptrs = _fb_outputs(dev, B, T, N, mask)
+    model = (nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0))
+    nbytes = L.hmm355_fb_workspace_bytes(B, T, N)
+    if lengths is not None:
+        lens = lengths.to(torch.int32).to(dev)
+        ws = ops._call(dev, L.hmm355_forward_backward_ragged_f32, *model, nat.ptr(log_beta_T), nat.ptr(lens),
+                       B, T, N, mask, *ptrs, ws=nbytes)
+    else:
+        ws = ops._call(dev, L.hmm355_forward_backward_plan_f32, *model, nat.ptr(plan), nat.ptr(log_beta_T),
+                       B, T, N, mask, *ptrs, ws=nbytes)
     rows = B * T
-    # the workspace pieces, at the offsets the library reports (hmm355_fb_workspace_layout)
+    # the workspace pieces, at the offsets the library reports (hmm355_fb_workspace_layout); they are
+    # views of ws, which lives as long as they do
     o = fb_layout(B, T, N)
     fl = ws.view(torch.float32)
     piece = lambda name, n: fl[o[name] // 4: o[name] // 4 + n]
@@ -237,17 +240,10 @@ def _run_tv_fb(log_obs, A, sb, st, log_p0, log_beta_T=None, posterior=False, out
     NP = _pad(N)
     dev = log_obs.device
     L = nat.lib()
-    ws = torch.empty(L.hmm355_tv_fb_workspace_bytes(B, T, N), dtype=torch.uint8, device=dev)
     mask = out_mask if out_mask is not None else (nat.FB_POSTERIOR if posterior else 0)
-    mk = lambda bit: torch.empty(B, T, N, device=dev) if mask & bit else None
-    post, fwd, bwd = mk(nat.FB_POSTERIOR), mk(nat.FB_FORWARD), mk(nat.FB_BACKWARD)
-    loglik = torch.empty(B, device=dev)
-    lik_ref = torch.empty(B, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_tv_forward_backward_ex_f32(
-            nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(log_p0), nat.ptr(log_beta_T), B, T, N,
-            mask, nat.ptr(post), nat.ptr(fwd), nat.ptr(bwd), nat.ptr(loglik), nat.ptr(lik_ref),
-            nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    (post, fwd, bwd, loglik, lik_ref), ptrs = _fb_outputs(dev, B, T, N, mask)
+    ws = ops._call(dev, L.hmm355_tv_forward_backward_ex_f32, nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(log_p0),
+                   nat.ptr(log_beta_T), B, T, N, mask, *ptrs, ws=L.hmm355_tv_fb_workspace_bytes(B, T, N))
     if out_mask is not None:
         post = (post, fwd, bwd)
     rows = B * T
@@ -413,11 +409,8 @@ class ForwardBackwardFn(torch.autograd.Function):
         srcW, Fw, srcZ, Fz = _adjoint_sources(U, V, E, post, fwd, bwd, gp, gf, gb, CA, CB)
         W = torch.empty(B, T, N, device=obs.device)
         P = torch.empty(B, T, N, device=obs.device)
-        L = nat.lib()
-        with torch.cuda.device(obs.device):
-            nat.check(L.hmm355_fb_adjoint_f32(nat.ptr(E), nat.ptr(lP), nat.ptr(srcW), nat.ptr(Fw), nat.ptr(srcZ),
-                                              nat.ptr(Fz), B, T, N, nat.ptr(W), nat.ptr(P),
-                                              nat.stream_of(obs.device)))
+        ops._call(obs.device, nat.lib().hmm355_fb_adjoint_f32, nat.ptr(E), nat.ptr(lP), nat.ptr(srcW), nat.ptr(Fw),
+                  nat.ptr(srcZ), nat.ptr(Fz), B, T, N, nat.ptr(W), nat.ptr(P))
         grad_lo = U * W + V * P
         grad_obs = grad_lo / (obs + 1e-8) if ctx.obs_mode == nat.OBS_PROB else grad_lo
         if valid is not None:
@@ -476,11 +469,8 @@ class TvForwardBackwardFn(torch.autograd.Function):
         srcW, Fw, srcZ, Fz = _adjoint_sources(U, V, E, post, fwd, bwd, got.get("p"), got.get("f"), got.get("b"))
         W = torch.empty(B, T, N, device=lo.device)
         P = torch.empty(B, T, N, device=lo.device)
-        L = nat.lib()
-        with torch.cuda.device(lo.device):
-            nat.check(L.hmm355_tv_fb_adjoint_f32(nat.ptr(E), nat.ptr(A), ctx.sb, ctx.st, nat.ptr(srcW), nat.ptr(Fw),
-                                                 nat.ptr(srcZ), nat.ptr(Fz), B, T, N, nat.ptr(W), nat.ptr(P),
-                                                 nat.stream_of(lo.device)))
+        ops._call(lo.device, nat.lib().hmm355_tv_fb_adjoint_f32, nat.ptr(E), nat.ptr(A), ctx.sb, ctx.st, nat.ptr(srcW),
+                  nat.ptr(Fw), nat.ptr(srcZ), nat.ptr(Fz), B, T, N, nat.ptr(W), nat.ptr(P))
         grad_lo = U * W + V * P
         grad_l0 = (U[:, 0] * W[:, 0]).sum(0)
         grad_A = None

@@ -4,6 +4,9 @@ Each op allocates its outputs (and the C ABI's workspace) through the torch cach
 allocator on the input's device and launches on the current HIP stream.  The ops are
 registered with torch.library so they are visible to torch.compile / export and have
 shape-only fake implementations; their only real implementation is the HIP library.
+An op's outputs are written once, in its `_<op>_outputs` spec, which the op and its fake both
+call; every native call goes through `_call` (workspace, stream, device, error check) and every
+lengths argument through `_lengths`.
 
   torch.ops.hmm355.forward_backward(obs, log_P, log_p0, obs_mode, out_mask)
       -> (posterior, forward, backward, loglik, lik_ref)
@@ -43,6 +46,7 @@ shape-only fake implementations; their only real implementation is the HIP libra
   torch.ops.hmm355.ffbs(fwd, log_P, uniforms, lengths) -> states (B,K,T)     posterior path samples
   torch.ops.hmm355.gmm_stats(x, weight, means, log_vars, log_w, mix_lse, lengths) -> (occ, sx, sxx)
 """
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -68,6 +72,7 @@ NARROW_MAX_STATES = nat.NARROW_MAX_STATES
 WIDE_MAX_STATES = nat.WIDE_MAX_STATES
 
 _EMPTY = (0,)
+_F32, _I64, _I32 = torch.float32, torch.int64, torch.int32
 
 
 def _f32c(t):
@@ -76,6 +81,58 @@ def _f32c(t):
 
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+# A spec `_<op>_outputs(mk, sizes..., wants...)` allocates each output with mk(shape, dtype=...): the op
+# passes _on(device), its fake x.new_empty.  It states every dtype (new_empty would inherit the
+# input's) and gives an output that is not wanted the empty shape _EMPTY (0 for the 1-D ones).
+def _on(device):
+    return functools.partial(torch.empty, device=device)
+
+
+def _scores_output(mk, B, T, S):
+    """The single fp32 (B,T,S) output of gmm_diag_logprob, semimarkov_quad and soft_dtw_grad."""
+    return mk((B, T, S), dtype=_F32)
+
+
+def _opt(t, want):
+    """Pointer of an optional output: NULL unless it is wanted."""
+    return nat.ptr(t) if want else None
+
+
+def _call(dev, fn, *args, ws=None):
+    """One native call on `dev`'s current stream, raised through nat.check: fn(*args, stream), or with
+    `ws` fn(*args, workspace, its bytes, stream).  ws is the workspace's size in bytes, allocated here,
+    or a workspace tensor to use again; the tensor is returned (callers that read it keep it)."""
+    if ws is None:
+        tail = ()
+    else:
+        if not isinstance(ws, Tensor):
+            ws = _workspace(ws, dev)
+        tail = (nat.ptr(ws), ws.numel())
+    with torch.cuda.device(dev):
+        nat.check(fn(*args, *tail, nat.stream_of(dev)))
+    return ws
+
+
+def _lengths(lengths, name, count, lo, hi, dev=None, integers=None):
+    """One lengths argument (a tensor on any device, a list or a numpy array) checked on the host
+    (ValueError): `count` values in [lo, hi].  integers: None takes any dtype (whole numbers in a
+    float tensor pass); "first" / "last" refuse a floating, complex or boolean one before / after
+    the count is checked (the order each caller has always had).  Returns (CPU int64 tensor, int32
+    tensor on `dev` or None without one).  Reading the values is one synchronisation."""
+    t = torch.as_tensor(lengths)
+    refused = integers is not None and (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+    if refused and integers == "first":
+        raise ValueError(f"{name} must hold integers; got {t.dtype}")
+    if t.numel() != count:
+        raise ValueError(f"{name} must hold one length per sequence ({count}); got {tuple(t.shape)}")
+    if refused:
+        raise ValueError(f"{name} must hold integers; got {t.dtype}")
+    host = t.detach().reshape(count).to("cpu", torch.int64)
+    if count and (int(host.min()) < lo or int(host.max()) > hi):
+        raise ValueError(f"{name} must lie in [{lo}, {hi}]; got {host.tolist()}")
+    return host, None if dev is None else host.to(torch.int32).to(dev)
 
 
 # ------------------------------------------------------------------ forward-backward
@@ -108,14 +165,13 @@ def make_plan(log_P: Tensor, read_banded: bool = True, dense: bool = False) -> O
     N = log_P.shape[0]
     L = nat.lib()
     plan = torch.empty(L.hmm355_plan_bytes(N), dtype=torch.uint8, device=log_P.device)
+    _call(log_P.device, L.hmm355_plan_ex_f32, nat.ptr(log_P), N, nat.PLAN_DENSE if dense else 0, nat.ptr(plan))
+    if not read_banded:
+        plan._hmm355_banded = None
+        return plan
+    # banded in both directions: forward_backward then runs both chains of a sequence in
+    # one workgroup (HMM355_FB_PAIR, csrc/fbpair.h).  One synchronous read per plan.
     with torch.cuda.device(log_P.device):
-        nat.check(L.hmm355_plan_ex_f32(nat.ptr(log_P), N, nat.PLAN_DENSE if dense else 0, nat.ptr(plan),
-                                       nat.stream_of(log_P.device)))
-        if not read_banded:
-            plan._hmm355_banded = None
-            return plan
-        # banded in both directions: forward_backward then runs both chains of a sequence in
-        # one workgroup (HMM355_FB_PAIR, csrc/fbpair.h).  One synchronous read per plan.
         banded = L.hmm355_plan_banded(nat.ptr(plan), nat.stream_of(log_P.device))
     if banded < 0:
         nat.check(banded)
@@ -168,6 +224,21 @@ def _use_pair(B: int, dev) -> bool:
     return B > _CUS[key] // 2
 
 
+def _fb_outputs(mk, B, T, N, out_mask):
+    """(posterior, forward, backward, loglik, lik_ref) of every forward-backward entry point."""
+    rows = (B, T, N)   # (written out, not looped: bench.py's step pays this host time)
+    return (mk(rows if out_mask & FB_POSTERIOR else _EMPTY, dtype=_F32),
+            mk(rows if out_mask & FB_FORWARD else _EMPTY, dtype=_F32),
+            mk(rows if out_mask & FB_BACKWARD else _EMPTY, dtype=_F32), mk(B, dtype=_F32), mk(B, dtype=_F32))
+
+
+def _fb_ptrs(outs, out_mask):
+    """The five output pointers as the forward-backward entry points take them."""
+    post, fwd, bwd, loglik, lik_ref = outs
+    return (nat.ptr(post) if out_mask & FB_POSTERIOR else None, nat.ptr(fwd) if out_mask & FB_FORWARD else None,
+            nat.ptr(bwd) if out_mask & FB_BACKWARD else None, nat.ptr(loglik), nat.ptr(lik_ref))
+
+
 @torch.library.custom_op("hmm355::forward_backward", mutates_args=())
 def forward_backward(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int,
                      out_mask: int, plan: Optional[Tensor] = None, pair: Optional[bool] = None,
@@ -183,49 +254,36 @@ def forward_backward(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int,
     B, T, N = obs.shape
     dev = obs.device
     L = nat.lib()
-    post = torch.empty((B, T, N) if out_mask & FB_POSTERIOR else _EMPTY, device=dev)
-    fwd = torch.empty((B, T, N) if out_mask & FB_FORWARD else _EMPTY, device=dev)
-    bwd = torch.empty((B, T, N) if out_mask & FB_BACKWARD else _EMPTY, device=dev)
-    loglik = torch.empty(B, device=dev)
-    lik_ref = torch.empty(B, device=dev)
+    outs = _fb_outputs(_on(dev), B, T, N, out_mask)
     if B == 0:
-        return post, fwd, bwd, loglik, lik_ref
+        return outs
     if _use_wide(N, wide):
-        ws = _workspace(L.hmm355_fb_wide_workspace_bytes(B, T, N), dev)
-        with torch.cuda.device(dev):
-            nat.check(L.hmm355_forward_backward_wide_f32(
-                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), B, T, N, out_mask & 7,
-                nat.ptr(post) if out_mask & FB_POSTERIOR else None,
-                nat.ptr(fwd) if out_mask & FB_FORWARD else None,
-                nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
-                nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-        return post, fwd, bwd, loglik, lik_ref
-    nbytes = L.hmm355_fb_workspace_bytes(B, T, N)
-    ws = _workspace(nbytes, dev)
+        _call(dev, L.hmm355_forward_backward_wide_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0),
+              B, T, N, out_mask & 7, *_fb_ptrs(outs, out_mask), ws=L.hmm355_fb_wide_workspace_bytes(B, T, N))
+        return outs
     banded = plan is not None and getattr(plan, "_hmm355_banded", False) is True
     use_pair = banded and (_use_pair(B, dev) if pair is None else pair)
     if use_pair:
         out_mask |= FB_PAIR
     elif banded and (out_mask & FB_POSTERIOR) and fb_follow_default(follow):
         out_mask |= FB_PLAN_BANDED
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_forward_backward_plan_f32(
-            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(plan), None, B, T, N, out_mask,
-            nat.ptr(post) if out_mask & FB_POSTERIOR else None,
-            nat.ptr(fwd) if out_mask & FB_FORWARD else None,
-            nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
-            nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return post, fwd, bwd, loglik, lik_ref
+    _call(dev, L.hmm355_forward_backward_plan_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0),
+          nat.ptr(plan), None, B, T, N, out_mask, *_fb_ptrs(outs, out_mask),
+          ws=L.hmm355_fb_workspace_bytes(B, T, N))
+    return outs
 
 
 @forward_backward.register_fake
 def _(obs, log_P, log_p0, obs_mode, out_mask, plan=None, pair=None, follow=None, wide=None):
-    B, T, N = obs.shape
-    mk = lambda bit: obs.new_empty((B, T, N) if out_mask & bit else _EMPTY)
-    return mk(FB_POSTERIOR), mk(FB_FORWARD), mk(FB_BACKWARD), obs.new_empty(B), obs.new_empty(B)
+    return _fb_outputs(obs.new_empty, *obs.shape, out_mask)
 
 
 # ---------------------------------------------------------------------------- Viterbi
+def _viterbi_outputs(mk, B, T, N):
+    """(states, log_delta, final_score) of viterbi and viterbi_ragged."""
+    return mk((B, T), dtype=_I64), mk((B, T, N), dtype=_F32), mk(B, dtype=_F32)
+
+
 @torch.library.custom_op("hmm355::viterbi", mutates_args=())
 def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
             plan: Optional[Tensor] = None, follow: Optional[bool] = None,
@@ -240,19 +298,14 @@ def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
     B, T, N = obs.shape
     dev = obs.device
     L = nat.lib()
-    states = torch.empty((B, T), dtype=torch.int64, device=dev)
-    delta = torch.empty((B, T, N), device=dev)
-    final = torch.empty(B, device=dev)
+    states, delta, final = outs = _viterbi_outputs(_on(dev), B, T, N)
     if B == 0:
-        return states, delta, final
+        return outs
     if _use_wide(N, wide):
-        ws = _workspace(L.hmm355_viterbi_wide_workspace_bytes(B, T, N, obs_mode), dev)
-        with torch.cuda.device(dev):
-            nat.check(L.hmm355_viterbi_wide_f32(
-                nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), B, T, N, nat.ptr(states), nat.ptr(delta),
-                nat.ptr(final), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-        return states, delta, final
-    ws = _workspace(L.hmm355_viterbi_workspace_bytes_ex(B, T, N, obs_mode), dev)
+        _call(dev, L.hmm355_viterbi_wide_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), B, T, N,
+              nat.ptr(states), nat.ptr(delta), nat.ptr(final),
+              ws=L.hmm355_viterbi_wide_workspace_bytes(B, T, N, obs_mode))
+        return outs
     flags = 0
     if plan is not None and follow is not False:
         if getattr(plan, "_hmm355_banded", False) is True:
@@ -262,17 +315,15 @@ def viterbi(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
             # (a plan whose structure the host never read,
             # make_plan(read_banded=False), asks for them too: on a banded matrix they return at once)
             flags = VIT_PLAN_DENSE
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_viterbi_plan_ex_f32(
-            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(plan), flags, B, T, N,
-            nat.ptr(states), nat.ptr(delta), nat.ptr(final), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return states, delta, final
+    _call(dev, L.hmm355_viterbi_plan_ex_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(plan),
+          flags, B, T, N, nat.ptr(states), nat.ptr(delta), nat.ptr(final),
+          ws=L.hmm355_viterbi_workspace_bytes_ex(B, T, N, obs_mode))
+    return outs
 
 
 @viterbi.register_fake
 def _(obs, log_P, init, obs_mode, plan=None, follow=None, wide=None):
-    B, T, N = obs.shape
-    return (obs.new_empty((B, T), dtype=torch.int64), obs.new_empty((B, T, N)), obs.new_empty(B))
+    return _viterbi_outputs(obs.new_empty, *obs.shape)
 
 
 # ------------------------------------------------------- padded batches with lengths
@@ -284,15 +335,7 @@ def ragged_lengths(lengths, B: int, T: int, N: Optional[int] = None) -> Tensor:
     workgroup per sequence (csrc/ragged.hip)."""
     if N is not None and N > NARROW_MAX_STATES:
         raise ValueError(f"per-sequence lengths are supported for at most {NARROW_MAX_STATES} states; got {N}")
-    t = torch.as_tensor(lengths)
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise ValueError(f"lengths must hold integers; got {t.dtype}")
-    if t.numel() != B:
-        raise ValueError(f"lengths must hold one length per sequence ({B}); got {tuple(t.shape)}")
-    host = t.detach().reshape(B).to("cpu", torch.int64)
-    if B and (int(host.min()) < 1 or int(host.max()) > T):
-        raise ValueError(f"lengths must lie in [1, {T}]; got {host.tolist()}")
-    return host
+    return _lengths(lengths, "lengths", B, 1, T, integers="first")[0]
 
 
 def active_lengths(lengths, B: int, T: int, N: Optional[int] = None) -> Optional[Tensor]:
@@ -344,28 +387,16 @@ def forward_backward_ragged(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode
     dev = obs.device
     lens = host.to(torch.int32).to(dev)
     L = nat.lib()
-    post = torch.empty((B, T, N) if out_mask & FB_POSTERIOR else _EMPTY, device=dev)
-    fwd = torch.empty((B, T, N) if out_mask & FB_FORWARD else _EMPTY, device=dev)
-    bwd = torch.empty((B, T, N) if out_mask & FB_BACKWARD else _EMPTY, device=dev)
-    loglik = torch.empty(B, device=dev)
-    lik_ref = torch.empty(B, device=dev)
-    ws = _workspace(L.hmm355_fb_workspace_bytes(B, T, N), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_forward_backward_ragged_f32(
-            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0), nat.ptr(lbt), nat.ptr(lens), B, T, N, out_mask,
-            nat.ptr(post) if out_mask & FB_POSTERIOR else None,
-            nat.ptr(fwd) if out_mask & FB_FORWARD else None,
-            nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
-            nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return post, fwd, bwd, loglik, lik_ref
+    outs = _fb_outputs(_on(dev), B, T, N, out_mask)
+    _call(dev, L.hmm355_forward_backward_ragged_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(log_p0),
+          nat.ptr(lbt), nat.ptr(lens), B, T, N, out_mask, *_fb_ptrs(outs, out_mask),
+          ws=L.hmm355_fb_workspace_bytes(B, T, N))
+    return outs
 
 
 @forward_backward_ragged.register_fake
 def _(obs, log_P, log_p0, obs_mode, lengths, out_mask, log_beta_T=None):
-    B, T, N = obs.shape
-    mk = lambda bit: obs.new_empty((B, T, N) if out_mask & bit else _EMPTY, dtype=torch.float32)
-    return (mk(FB_POSTERIOR), mk(FB_FORWARD), mk(FB_BACKWARD), obs.new_empty(B, dtype=torch.float32),
-            obs.new_empty(B, dtype=torch.float32))
+    return _fb_outputs(obs.new_empty, *obs.shape, out_mask)
 
 
 @torch.library.custom_op("hmm355::viterbi_ragged", mutates_args=())
@@ -387,25 +418,24 @@ def viterbi_ragged(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
     dev = obs.device
     lens = host.to(torch.int32).to(dev)
     L = nat.lib()
-    states = torch.empty((B, T), dtype=torch.int64, device=dev)
-    delta = torch.empty((B, T, N), device=dev)
-    final = torch.empty(B, device=dev)
-    ws = _workspace(L.hmm355_viterbi_ragged_workspace_bytes(B, T, N, obs_mode), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_viterbi_ragged_f32(
-            nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(lens), B, T, N, nat.ptr(states),
-            nat.ptr(delta), nat.ptr(final), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return states, delta, final
+    states, delta, final = outs = _viterbi_outputs(_on(dev), B, T, N)
+    _call(dev, L.hmm355_viterbi_ragged_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(lens),
+          B, T, N, nat.ptr(states), nat.ptr(delta), nat.ptr(final),
+          ws=L.hmm355_viterbi_ragged_workspace_bytes(B, T, N, obs_mode))
+    return outs
 
 
 @viterbi_ragged.register_fake
 def _(obs, log_P, init, obs_mode, lengths):
-    B, T, N = obs.shape
-    return (obs.new_empty((B, T), dtype=torch.int64), obs.new_empty((B, T, N), dtype=torch.float32),
-            obs.new_empty(B, dtype=torch.float32))
+    return _viterbi_outputs(obs.new_empty, *obs.shape)
 
 
 # ------------------------------------------------------------------- GMM emission
+def _gmm_stats_outputs(mk, S, C, D):
+    """(occ, sx, sxx)."""
+    return mk((S, C), dtype=_F32), mk((S, C, D), dtype=_F32), mk((S, C, D), dtype=_F32)
+
+
 @torch.library.custom_op("hmm355::gmm_diag_logprob", mutates_args=())
 def gmm_diag_logprob(x: Tensor, means: Tensor, log_vars: Tensor, log_w: Tensor, mix_lse: int) -> Tensor:
     nat.require_gpu(x, means, log_vars, log_w)
@@ -414,21 +444,18 @@ def gmm_diag_logprob(x: Tensor, means: Tensor, log_vars: Tensor, log_w: Tensor, 
     S, C, D2 = means.shape
     if D2 != D:
         raise ValueError(f"feature dim mismatch: x has {D}, means have {D2}")
-    out = torch.empty((B, T, S), device=x.device)
+    out = _scores_output(_on(x.device), B, T, S)
     if B * T == 0:
         return out
     L = nat.lib()
-    ws = _workspace(L.hmm355_gmm_workspace_bytes(B, T, D, S, C), x.device)
-    with torch.cuda.device(x.device):
-        nat.check(L.hmm355_gmm_diag_logprob_f32(
-            nat.ptr(x), nat.ptr(means), nat.ptr(log_vars), nat.ptr(log_w), B, T, D, S, C, mix_lse,
-            nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream_of(x.device)))
+    _call(x.device, L.hmm355_gmm_diag_logprob_f32, nat.ptr(x), nat.ptr(means), nat.ptr(log_vars), nat.ptr(log_w),
+          B, T, D, S, C, mix_lse, nat.ptr(out), ws=L.hmm355_gmm_workspace_bytes(B, T, D, S, C))
     return out
 
 
 @gmm_diag_logprob.register_fake
 def _(x, means, log_vars, log_w, mix_lse):
-    return x.new_empty((x.shape[0], x.shape[1], means.shape[0]))
+    return _scores_output(x.new_empty, x.shape[0], x.shape[1], means.shape[0])
 
 
 @torch.library.custom_op("hmm355::gmm_stats", mutates_args=())
@@ -464,29 +491,28 @@ def gmm_stats(x: Tensor, weight: Tensor, means: Tensor, log_vars: Tensor, log_w:
     nat.require_gpu(x, weight, means, log_vars, log_w)
     x, weight, means, log_vars, log_w = (_f32c(t.detach()) for t in (x, weight, means, log_vars, log_w))
     dev = x.device
-    if B * T == 0:
-        return torch.zeros((S, C), device=dev), torch.zeros((S, C, D), device=dev), torch.zeros((S, C, D), device=dev)
-    occ = torch.empty((S, C), device=dev)
-    sx = torch.empty((S, C, D), device=dev)
-    sxx = torch.empty((S, C, D), device=dev)
+    if B * T == 0:   # no frame: the sums are zero
+        return _gmm_stats_outputs(functools.partial(torch.zeros, device=dev), S, C, D)
+    occ, sx, sxx = outs = _gmm_stats_outputs(_on(dev), S, C, D)
     lens = None if host is None else host.to(torch.int32).to(dev)
     L = nat.lib()
-    ws = _workspace(L.hmm355_gmm_stats_workspace_bytes(B, T, D, S, C), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_gmm_stats_f32(
-            nat.ptr(x), nat.ptr(weight), nat.ptr(means), nat.ptr(log_vars), nat.ptr(log_w), nat.ptr(lens), B, T, D, S,
-            C, int(mix_lse), nat.ptr(occ), nat.ptr(sx), nat.ptr(sxx), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return occ, sx, sxx
+    _call(dev, L.hmm355_gmm_stats_f32, nat.ptr(x), nat.ptr(weight), nat.ptr(means), nat.ptr(log_vars),
+          nat.ptr(log_w), nat.ptr(lens), B, T, D, S, C, int(mix_lse), nat.ptr(occ), nat.ptr(sx), nat.ptr(sxx),
+          ws=L.hmm355_gmm_stats_workspace_bytes(B, T, D, S, C))
+    return outs
 
 
 @gmm_stats.register_fake
 def _(x, weight, means, log_vars, log_w, mix_lse, lengths=None):
-    S, C, D = means.shape
-    mk = lambda *shape: x.new_empty(shape, dtype=torch.float32)
-    return mk(S, C), mk(S, C, D), mk(S, C, D)
+    return _gmm_stats_outputs(x.new_empty, *means.shape)
 
 
 # ------------------------------------------------------------------------------- HSMM
+def _hsmm_viterbi_outputs(mk, B, T):
+    """(states, scores)."""
+    return mk((B, T), dtype=_I64), mk(B, dtype=_F32)
+
+
 @torch.library.custom_op("hmm355::hsmm_viterbi", mutates_args=())
 def hsmm_viterbi(lp: Tensor, dur_lp: Tensor, log_T: Tensor, flags: int = 0) -> Tuple[Tensor, Tensor]:
     """flags: kernel-form flags (FORM_GENERAL, FORM_SERIAL_WALK; identical results)."""
@@ -495,25 +521,18 @@ def hsmm_viterbi(lp: Tensor, dur_lp: Tensor, log_T: Tensor, flags: int = 0) -> T
     B, T, S = lp.shape
     Dm = dur_lp.shape[1]
     dev = lp.device
-    states = torch.empty((B, T), dtype=torch.int64, device=dev)
-    scores = torch.empty(B, device=dev)
+    states, scores = outs = _hsmm_viterbi_outputs(_on(dev), B, T)
     if B == 0:
-        return states, scores
+        return outs
     L = nat.lib()
     # The general form (S or Dmax beyond the register-slot kernels) keeps a (B,T,S,Dmax+1) fp32
     # table: checked against the device's free memory up front, and decoded in batch slices
     # that fit when the whole batch does not (sequences are independent).
     wsb = lambda b_, t_, s_, d_: L.hmm355_hsmm_workspace_bytes_ex(b_, t_, s_, d_, flags)
-    Bc = _ws_batch(wsb, B, T, S, Dm, dev, "HSMM decode")
-    ws = _workspace(wsb(Bc, T, S, Dm), dev)
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, Bc):
-            nb = min(Bc, B - b0)
-            nat.check(L.hmm355_hsmm_viterbi_ex_f32(
-                nat.ptr(lp[b0:b0 + nb]), nat.ptr(dur_lp), nat.ptr(log_T), nb, T, S, Dm, flags,
-                nat.ptr(states[b0:b0 + nb]), nat.ptr(scores[b0:b0 + nb]), nat.ptr(ws), ws.numel(),
-                nat.stream_of(dev)))
-    return states, scores
+    _call_slices(dev, L.hmm355_hsmm_viterbi_ex_f32, wsb, "HSMM decode", B, T, S, Dm, lambda sl, nb: (
+        nat.ptr(lp[sl]), nat.ptr(dur_lp), nat.ptr(log_T), nb, T, S, Dm, flags, nat.ptr(states[sl]),
+        nat.ptr(scores[sl])))
+    return outs
 
 
 _HSMM_WS_CHECK_BYTES = 1 << 30  # workspaces above this are checked against free device memory
@@ -536,10 +555,22 @@ def _ws_batch(ws_bytes, B, T, S, Dm, dev, what):
     return max(1, min(B, int(0.9 * avail) // per_seq))
 
 
+def _call_slices(dev, fn, ws_bytes, what, B, T, S, Dm, args, cap=None):
+    """fn over the batch in slices whose workspace fits the device (_ws_batch; at most `cap`
+    sequences each), all in one workspace.  args(sl, nb) gives the call's leading arguments for
+    the nb sequences of the slice sl."""
+    Bc = _ws_batch(ws_bytes, B, T, S, Dm, dev, what)
+    if cap is not None:
+        Bc = max(1, min(Bc, cap))
+    ws = _workspace(ws_bytes(Bc, T, S, Dm), dev)
+    for b0 in range(0, B, Bc):
+        sl = slice(b0, min(b0 + Bc, B))
+        _call(dev, fn, *args(sl, sl.stop - b0), ws=ws)
+
+
 @hsmm_viterbi.register_fake
 def _(lp, dur_lp, log_T, flags=0):
-    B, T, S = lp.shape
-    return lp.new_empty((B, T), dtype=torch.int64), lp.new_empty(B)
+    return _hsmm_viterbi_outputs(lp.new_empty, lp.shape[0], lp.shape[1])
 
 
 HSMM_FB_MAX_STATES = nat.HSMM_FB_MAX_STATES
@@ -551,6 +582,13 @@ def hsmm_fb_supported(S: int, Dm: int) -> bool:
     """The sizes hsmm_forward_backward takes (csrc/hsmm_fb.hip: a sequence's open segments live in
     64 KiB of LDS)."""
     return 1 <= S <= HSMM_FB_MAX_STATES and 1 <= Dm <= HSMM_FB_MAX_DURATION and S * Dm <= HSMM_FB_MAX_CELLS
+
+
+def _hsmm_fb_outputs(mk, B, T, S, Dm, want_gamma, want_dur, want_trans, want_init):
+    """(loglik, gamma, dur_counts, trans_counts, init_post)."""
+    return (mk(B, dtype=_F32), mk((B, T, S) if want_gamma else _EMPTY, dtype=_F32),
+            mk((B, S, Dm) if want_dur else _EMPTY, dtype=_F32), mk((B, S, S) if want_trans else _EMPTY, dtype=_F32),
+            mk((B, S) if want_init else _EMPTY, dtype=_F32))
 
 
 @torch.library.custom_op("hmm355::hsmm_forward_backward", mutates_args=())
@@ -573,11 +611,8 @@ def hsmm_forward_backward(lp: Tensor, dur_lp: Tensor, log_T: Tensor, log_init: O
         raise ValueError(f"hsmm_forward_backward: lp {tuple(lp.shape)}, dur_lp {tuple(dur_lp.shape)}, log_T "
                          f"{tuple(log_T.shape)} and log_init do not agree on the number of states")
     dev = lp.device
-    loglik = torch.empty(B, device=dev)
-    gamma = torch.empty((B, T, S) if want_gamma else _EMPTY, device=dev)
-    dur_counts = torch.empty((B, S, Dm) if want_dur else _EMPTY, device=dev)
-    trans_counts = torch.empty((B, S, S) if want_trans else _EMPTY, device=dev)
-    init_post = torch.empty((B, S) if want_init else _EMPTY, device=dev)
+    wants = (want_gamma, want_dur, want_trans, want_init)
+    loglik, *counts = outs = _hsmm_fb_outputs(_on(dev), B, T, S, Dm, *wants)
     L = nat.lib()
     fl = (int(flags) | (nat.HSMM_FB_GAMMA if want_gamma else 0) | (nat.HSMM_FB_DUR if want_dur else 0) |
           (nat.HSMM_FB_TRANS if want_trans else 0) | (nat.HSMM_FB_INIT if want_init else 0))
@@ -585,32 +620,20 @@ def hsmm_forward_backward(lp: Tensor, dur_lp: Tensor, log_T: Tensor, log_init: O
         # the native call names what is wrong with the shape (nothing is launched)
         nat.check(L.hmm355_hsmm_fb_f32(None, None, None, None, B, T, S, Dm, fl, None, None, None, None, None,
                                        None, 0, None))
-        return loglik, gamma, dur_counts, trans_counts, init_post
+        return outs
     wsb = lambda b_, t_, s_, d_: L.hmm355_hsmm_fb_workspace_bytes(b_, t_, s_, d_, fl)
-    Bc = _ws_batch(wsb, B, T, S, Dm, dev, "HSMM forward-backward")
-    Bc = max(1, min(Bc, nat.HSMM_FB_MAX_BATCH, (1 << 31) // T))  # the native call's limits on B and B * T
-    ws = _workspace(wsb(Bc, T, S, Dm), dev)
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, Bc):
-            nb = min(Bc, B - b0)
-            nat.check(L.hmm355_hsmm_fb_f32(
-                nat.ptr(lp[b0:b0 + nb]), nat.ptr(dur_lp), nat.ptr(log_T), nat.ptr(log_init), nb, T, S, Dm, fl,
-                nat.ptr(loglik[b0:b0 + nb]), nat.ptr(gamma[b0:b0 + nb]) if want_gamma else None,
-                nat.ptr(dur_counts[b0:b0 + nb]) if want_dur else None,
-                nat.ptr(trans_counts[b0:b0 + nb]) if want_trans else None,
-                nat.ptr(init_post[b0:b0 + nb]) if want_init else None, nat.ptr(ws), ws.numel(),
-                nat.stream_of(dev)))
-    return loglik, gamma, dur_counts, trans_counts, init_post
+    _call_slices(dev, L.hmm355_hsmm_fb_f32, wsb, "HSMM forward-backward", B, T, S, Dm, lambda sl, nb: (
+        nat.ptr(lp[sl]), nat.ptr(dur_lp), nat.ptr(log_T), nat.ptr(log_init), nb, T, S, Dm, fl, nat.ptr(loglik[sl]),
+        *[_opt(o[sl], want) for o, want in zip(counts, wants)]),
+        cap=min(nat.HSMM_FB_MAX_BATCH, (1 << 31) // T))   # the native call's limits on B and B * T
+    return outs
 
 
 @hsmm_forward_backward.register_fake
 def _(lp, dur_lp, log_T, log_init=None, *, want_gamma=False, want_dur=False, want_trans=False, want_init=False,
       flags=0):
     B, T, S = lp.shape
-    Dm = dur_lp.shape[1]
-    return (lp.new_empty(B), lp.new_empty((B, T, S) if want_gamma else _EMPTY),
-            lp.new_empty((B, S, Dm) if want_dur else _EMPTY), lp.new_empty((B, S, S) if want_trans else _EMPTY),
-            lp.new_empty((B, S) if want_init else _EMPTY))
+    return _hsmm_fb_outputs(lp.new_empty, B, T, S, dur_lp.shape[1], want_gamma, want_dur, want_trans, want_init)
 
 
 # ------------------------------------------------- time-varying transitions (NeuralHMM)
@@ -645,30 +668,23 @@ def tv_forward_backward(log_obs: Tensor, log_A: Tensor, log_p0: Tensor,
     B, T, N = log_obs.shape
     dev = log_obs.device
     L = nat.lib()
-    post = torch.empty((B, T, N) if out_mask & FB_POSTERIOR else _EMPTY, device=dev)
-    fwd = torch.empty((B, T, N) if out_mask & FB_FORWARD else _EMPTY, device=dev)
-    bwd = torch.empty((B, T, N) if out_mask & FB_BACKWARD else _EMPTY, device=dev)
-    loglik = torch.empty(B, device=dev)
-    lik_ref = torch.empty(B, device=dev)
+    outs = _fb_outputs(_on(dev), B, T, N, out_mask)
     if B == 0:
-        return post, fwd, bwd, loglik, lik_ref
+        return outs
     A, sb, st = _tv_matrix(log_A, B, T, N)
-    ws = _workspace(L.hmm355_tv_fb_workspace_bytes(B, T, N), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_tv_forward_backward_f32(
-            nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(log_p0), B, T, N, out_mask,
-            nat.ptr(post) if out_mask & FB_POSTERIOR else None,
-            nat.ptr(fwd) if out_mask & FB_FORWARD else None,
-            nat.ptr(bwd) if out_mask & FB_BACKWARD else None,
-            nat.ptr(loglik), nat.ptr(lik_ref), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return post, fwd, bwd, loglik, lik_ref
+    _call(dev, L.hmm355_tv_forward_backward_f32, nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(log_p0), B, T, N,
+          out_mask, *_fb_ptrs(outs, out_mask), ws=L.hmm355_tv_fb_workspace_bytes(B, T, N))
+    return outs
 
 
 @tv_forward_backward.register_fake
 def _(log_obs, log_A, log_p0, out_mask):
-    B, T, N = log_obs.shape
-    mk = lambda bit: log_obs.new_empty((B, T, N) if out_mask & bit else _EMPTY)
-    return mk(FB_POSTERIOR), mk(FB_FORWARD), mk(FB_BACKWARD), log_obs.new_empty(B), log_obs.new_empty(B)
+    return _fb_outputs(log_obs.new_empty, *log_obs.shape, out_mask)
+
+
+def _tv_viterbi_outputs(mk, B, T, N):
+    """(states, log_delta)."""
+    return mk((B, T), dtype=_I64), mk((B, T, N), dtype=_F32)
 
 
 @torch.library.custom_op("hmm355::tv_viterbi", mutates_args=())
@@ -677,24 +693,19 @@ def tv_viterbi(log_obs: Tensor, log_A: Tensor, init: Tensor) -> Tuple[Tensor, Te
     log_obs, init = _f32c(log_obs), _f32c(init)
     B, T, N = log_obs.shape
     dev = log_obs.device
-    states = torch.empty((B, T), dtype=torch.int64, device=dev)
-    delta = torch.empty((B, T, N), device=dev)
+    states, delta = outs = _tv_viterbi_outputs(_on(dev), B, T, N)
     if B == 0:
-        return states, delta
+        return outs
     A, sb, st = _tv_matrix(log_A, B, T, N)
     L = nat.lib()
-    ws = _workspace(L.hmm355_tv_viterbi_workspace_bytes(B, T, N), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_tv_viterbi_f32(
-            nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(init), B, T, N, nat.ptr(states), nat.ptr(delta),
-            nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return states, delta
+    _call(dev, L.hmm355_tv_viterbi_f32, nat.ptr(log_obs), nat.ptr(A), sb, st, nat.ptr(init), B, T, N,
+          nat.ptr(states), nat.ptr(delta), ws=L.hmm355_tv_viterbi_workspace_bytes(B, T, N))
+    return outs
 
 
 @tv_viterbi.register_fake
 def _(log_obs, log_A, init):
-    B, T, N = log_obs.shape
-    return log_obs.new_empty((B, T), dtype=torch.int64), log_obs.new_empty((B, T, N))
+    return _tv_viterbi_outputs(log_obs.new_empty, *log_obs.shape)
 
 
 # ------------------------------------------------------- explicit-duration (semi-Markov)
@@ -708,17 +719,15 @@ def semimarkov_quad(x: Tensor, means_t: Tensor, vars_t: Tensor) -> Tensor:
     if means_t.shape[0] != Df or tuple(vars_t.shape) != tuple(means_t.shape):
         raise ValueError(f"feature dim mismatch: x has {Df}, means {tuple(means_t.shape)}, "
                          f"variances {tuple(vars_t.shape)} (expected ({Df}, S))")
-    q = torch.empty((B, T, S), device=x.device)
-    with torch.cuda.device(x.device):
-        nat.check(nat.lib().hmm355_semimarkov_quad_f32(
-            nat.ptr(x), nat.ptr(means_t), nat.ptr(vars_t), B, T, Df, S, nat.ptr(q),
-            nat.stream_of(x.device)))
+    q = _scores_output(_on(x.device), B, T, S)
+    _call(x.device, nat.lib().hmm355_semimarkov_quad_f32, nat.ptr(x), nat.ptr(means_t), nat.ptr(vars_t), B, T, Df, S,
+          nat.ptr(q))
     return q
 
 
 @semimarkov_quad.register_fake
 def _(x, means_t, vars_t):
-    return x.new_empty((x.shape[0], x.shape[1], means_t.shape[1]))
+    return _scores_output(x.new_empty, x.shape[0], x.shape[1], means_t.shape[1])
 
 
 def _smk_args(quad, seg_const, log_init, log_T, dur_lp):
@@ -734,6 +743,16 @@ def _smk_args(quad, seg_const, log_init, log_T, dur_lp):
     return quad, seg_const, log_init, log_T, dur_lp, B, T, S, dur_lp.shape[1]
 
 
+def _smk_viterbi_outputs(mk, B, T):
+    """(seg_states, seg_durs, seg_count, scores); the op zeroes seg_count."""
+    return mk((B, T), dtype=_I64), mk((B, T), dtype=_I64), mk(B, dtype=_I32), mk(B, dtype=_F32)
+
+
+def _smk_forward_outputs(mk, B, T, S, Dm, want_alpha):
+    """(log_prob, log_alpha)."""
+    return mk(B, dtype=_F32), mk((B, T, S, Dm) if want_alpha else _EMPTY, dtype=_F32)
+
+
 @torch.library.custom_op("hmm355::semimarkov_viterbi", mutates_args=())
 def semimarkov_viterbi(quad: Tensor, seg_const: Optional[Tensor], log_init: Tensor, log_T: Tensor,
                        dur_lp: Tensor, flags: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -741,31 +760,21 @@ def semimarkov_viterbi(quad: Tensor, seg_const: Optional[Tensor], log_init: Tens
     scores (B).  flags: FORM_GENERAL forces the general form (identical results)."""
     quad, seg_const, log_init, log_T, dur_lp, B, T, S, Dm = _smk_args(quad, seg_const, log_init, log_T, dur_lp)
     dev = quad.device
-    seg_s = torch.empty((B, T), dtype=torch.int64, device=dev)
-    seg_d = torch.empty((B, T), dtype=torch.int64, device=dev)
-    cnt = torch.zeros(B, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, device=dev)
+    seg_s, seg_d, cnt, scores = outs = _smk_viterbi_outputs(_on(dev), B, T)
+    cnt.zero_()
     if B == 0:
-        return seg_s, seg_d, cnt, scores
+        return outs
     L = nat.lib()
     wsb = lambda b_, t_, s_, d_: L.hmm355_semimarkov_workspace_bytes_ex(b_, t_, s_, d_, flags)
-    Bc = _ws_batch(wsb, B, T, S, Dm, dev, "semi-Markov decode")
-    ws = _workspace(wsb(Bc, T, S, Dm), dev)
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, Bc):
-            nb = min(Bc, B - b0)
-            nat.check(L.hmm355_semimarkov_viterbi_ex_f32(
-                nat.ptr(quad[b0:b0 + nb]), nat.ptr(seg_const), nat.ptr(log_init), nat.ptr(log_T), nat.ptr(dur_lp),
-                nb, T, S, Dm, flags, nat.ptr(seg_s[b0:b0 + nb]), nat.ptr(seg_d[b0:b0 + nb]), nat.ptr(cnt[b0:b0 + nb]),
-                nat.ptr(scores[b0:b0 + nb]), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return seg_s, seg_d, cnt, scores
+    _call_slices(dev, L.hmm355_semimarkov_viterbi_ex_f32, wsb, "semi-Markov decode", B, T, S, Dm, lambda sl, nb: (
+        nat.ptr(quad[sl]), nat.ptr(seg_const), nat.ptr(log_init), nat.ptr(log_T), nat.ptr(dur_lp), nb, T, S, Dm,
+        flags, nat.ptr(seg_s[sl]), nat.ptr(seg_d[sl]), nat.ptr(cnt[sl]), nat.ptr(scores[sl])))
+    return outs
 
 
 @semimarkov_viterbi.register_fake
 def _(quad, seg_const, log_init, log_T, dur_lp, flags=0):
-    B, T, _ = quad.shape
-    return (quad.new_empty((B, T), dtype=torch.int64), quad.new_empty((B, T), dtype=torch.int64),
-            quad.new_empty(B, dtype=torch.int32), quad.new_empty(B))
+    return _smk_viterbi_outputs(quad.new_empty, quad.shape[0], quad.shape[1])
 
 
 @torch.library.custom_op("hmm355::semimarkov_forward", mutates_args=())
@@ -774,32 +783,30 @@ def semimarkov_forward(quad: Tensor, seg_const: Optional[Tensor], log_init: Tens
     """-> log_prob (B), log_alpha (B,T,S,Dmax) (empty (0,) unless want_alpha)."""
     quad, seg_const, log_init, log_T, dur_lp, B, T, S, Dm = _smk_args(quad, seg_const, log_init, log_T, dur_lp)
     dev = quad.device
-    lp = torch.empty(B, device=dev)
-    alpha = torch.empty((B, T, S, Dm) if want_alpha else (0,), device=dev)
+    lp, alpha = outs = _smk_forward_outputs(_on(dev), B, T, S, Dm, want_alpha)
     if B == 0:
-        return lp, alpha
+        return outs
     L = nat.lib()
     wsb = lambda b_, t_, s_, d_: L.hmm355_semimarkov_workspace_bytes_ex(b_, t_, s_, d_, flags)
-    Bc = _ws_batch(wsb, B, T, S, Dm, dev, "semi-Markov forward")
-    ws = _workspace(wsb(Bc, T, S, Dm), dev)
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, Bc):
-            nb = min(Bc, B - b0)
-            nat.check(L.hmm355_semimarkov_forward_ex_f32(
-                nat.ptr(quad[b0:b0 + nb]), nat.ptr(seg_const), nat.ptr(log_init), nat.ptr(log_T), nat.ptr(dur_lp),
-                nb, T, S, Dm, flags, nat.ptr(alpha[b0:b0 + nb]) if want_alpha else None, nat.ptr(lp[b0:b0 + nb]),
-                nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return lp, alpha
+    _call_slices(dev, L.hmm355_semimarkov_forward_ex_f32, wsb, "semi-Markov forward", B, T, S, Dm, lambda sl, nb: (
+        nat.ptr(quad[sl]), nat.ptr(seg_const), nat.ptr(log_init), nat.ptr(log_T), nat.ptr(dur_lp), nb, T, S, Dm,
+        flags, _opt(alpha[sl], want_alpha), nat.ptr(lp[sl])))
+    return outs
 
 
 @semimarkov_forward.register_fake
 def _(quad, seg_const, log_init, log_T, dur_lp, want_alpha, flags=0):
-    B, T, S = quad.shape
-    return quad.new_empty(B), quad.new_empty((B, T, S, dur_lp.shape[1]) if want_alpha else (0,))
+    return _smk_forward_outputs(quad.new_empty, *quad.shape, dur_lp.shape[1], want_alpha)
 
 
 # ------------------------------------------------------------------ streaming decoders
 STREAM_SLOTS = 32   # hypothesis slots per stream (max beam width; 16 when N > 128)
+
+
+def _stream_greedy_outputs(mk, B, T):
+    """(states, step scores)."""
+    return mk((B, T), dtype=_I64), mk((B, T), dtype=_F32)
+
 
 @torch.library.custom_op("hmm355::stream_greedy", mutates_args=())
 def stream_greedy(emis: Tensor, log_T: Tensor, prev_state: Tensor, log_n: float) -> Tuple[Tensor, Tensor]:
@@ -809,19 +816,15 @@ def stream_greedy(emis: Tensor, log_T: Tensor, prev_state: Tensor, log_n: float)
     emis, log_T = _f32c(emis), _f32c(log_T)
     prev_state = prev_state.to(torch.int32).contiguous()
     B, T, N = emis.shape
-    states = torch.empty((B, T), dtype=torch.int64, device=emis.device)
-    scores = torch.empty((B, T), device=emis.device)
-    with torch.cuda.device(emis.device):
-        nat.check(nat.lib().hmm355_stream_greedy_f32(
-            nat.ptr(emis), nat.ptr(log_T), nat.ptr(prev_state), float(log_n), B, T, N,
-            nat.ptr(states), nat.ptr(scores), nat.stream_of(emis.device)))
-    return states, scores
+    states, scores = outs = _stream_greedy_outputs(_on(emis.device), B, T)
+    _call(emis.device, nat.lib().hmm355_stream_greedy_f32, nat.ptr(emis), nat.ptr(log_T), nat.ptr(prev_state),
+          float(log_n), B, T, N, nat.ptr(states), nat.ptr(scores))
+    return outs
 
 
 @stream_greedy.register_fake
 def _(emis, log_T, prev_state, log_n):
-    B, T, _ = emis.shape
-    return emis.new_empty((B, T), dtype=torch.int64), emis.new_empty((B, T))
+    return _stream_greedy_outputs(emis.new_empty, emis.shape[0], emis.shape[1])
 
 
 def stream_beam(emis: Tensor, log_T: Tensor, beam_width: int, hyp_score: Tensor, hyp_last: Tensor,
@@ -846,11 +849,9 @@ def stream_beam(emis: Tensor, log_T: Tensor, beam_width: int, hyp_score: Tensor,
     states = torch.empty((B, T), dtype=torch.int64, device=dev)
     parent = torch.empty((B, T, K), dtype=torch.int16, device=dev)
     hstate = torch.empty((B, T, K), dtype=torch.int16, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().hmm355_stream_beam_f32(
-            nat.ptr(emis), nat.ptr(log_T), B, T, N, K, int(live_max), nat.ptr(hyp_score), nat.ptr(hyp_last),
-            nat.ptr(hyp_count), nat.ptr(first), nat.ptr(parent), nat.ptr(hstate), nat.ptr(states),
-            nat.stream_of(dev)))
+    _call(dev, nat.lib().hmm355_stream_beam_f32, nat.ptr(emis), nat.ptr(log_T), B, T, N, K, int(live_max),
+          nat.ptr(hyp_score), nat.ptr(hyp_last), nat.ptr(hyp_count), nat.ptr(first), nat.ptr(parent), nat.ptr(hstate),
+          nat.ptr(states))
     return states, parent, hstate
 
 
@@ -885,6 +886,18 @@ def _dtw_lens(dist, n_len, m_len):
     return out
 
 
+def _dtw_outputs(mk, B, N, M, want_cost, want_path):
+    """(cost_matrix, total, path_i, path_j, path_len)."""
+    path = (B, N + M - 1) if want_path else _EMPTY
+    return (mk((B, N, M) if want_cost else _EMPTY, dtype=_F32), mk(B, dtype=_F32), mk(path, dtype=_I32),
+            mk(path, dtype=_I32), mk(B if want_path else 0, dtype=_I32))
+
+
+def _soft_dtw_outputs(mk, B, N, M):
+    """(R, total)."""
+    return mk((B, N + 1, M + 1), dtype=_F32), mk(B, dtype=_F32)
+
+
 @torch.library.custom_op("hmm355::dtw", mutates_args=())
 def dtw(dist: Tensor, pattern: int, n_len: Optional[Tensor] = None, m_len: Optional[Tensor] = None,
         want_cost: bool = True, want_path: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
@@ -900,36 +913,20 @@ def dtw(dist: Tensor, pattern: int, n_len: Optional[Tensor] = None, m_len: Optio
     dev = dist.device
     if N < 1 or M < 1:
         raise ValueError(f"dist must have at least one row and one column; got {tuple(dist.shape)}")
-    P = N + M - 1
-    cost = torch.empty((B, N, M) if want_cost else _EMPTY, device=dev)
-    total = torch.empty(B, device=dev)
-    path_i = torch.empty((B, P) if want_path else _EMPTY, dtype=torch.int32, device=dev)
-    path_j = torch.empty((B, P) if want_path else _EMPTY, dtype=torch.int32, device=dev)
-    path_len = torch.empty(B if want_path else 0, dtype=torch.int32, device=dev)
+    cost, total, path_i, path_j, path_len = outs = _dtw_outputs(_on(dev), B, N, M, want_cost, want_path)
     if B == 0:
-        return cost, total, path_i, path_j, path_len
+        return outs
     L = nat.lib()
     flags = nat.DTW_PATH if want_path else 0
-    ws = _workspace(L.hmm355_dtw_workspace_bytes(B, N, M, flags), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_dtw_f32(
-            nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, int(pattern), flags,
-            nat.ptr(cost) if want_cost else None, nat.ptr(total),
-            nat.ptr(path_i) if want_path else None, nat.ptr(path_j) if want_path else None,
-            nat.ptr(path_len) if want_path else None, nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return cost, total, path_i, path_j, path_len
+    _call(dev, L.hmm355_dtw_f32, nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, int(pattern), flags,
+          _opt(cost, want_cost), nat.ptr(total), _opt(path_i, want_path), _opt(path_j, want_path),
+          _opt(path_len, want_path), ws=L.hmm355_dtw_workspace_bytes(B, N, M, flags))
+    return outs
 
 
 @dtw.register_fake
 def _(dist, pattern, n_len=None, m_len=None, want_cost=True, want_path=True):
-    B, N, M = dist.shape
-    P = N + M - 1
-    i32 = torch.int32
-    return (dist.new_empty((B, N, M) if want_cost else _EMPTY, dtype=torch.float32),
-            dist.new_empty(B, dtype=torch.float32),
-            dist.new_empty((B, P) if want_path else _EMPTY, dtype=i32),
-            dist.new_empty((B, P) if want_path else _EMPTY, dtype=i32),
-            dist.new_empty(B if want_path else 0, dtype=i32))
+    return _dtw_outputs(dist.new_empty, *dist.shape, want_cost, want_path)
 
 
 @torch.library.custom_op("hmm355::soft_dtw", mutates_args=())
@@ -943,18 +940,15 @@ def soft_dtw(dist: Tensor, gamma: float, n_len: Optional[Tensor] = None,
     dev = dist.device
     if N < 1 or M < 1:
         raise ValueError(f"dist must have at least one row and one column; got {tuple(dist.shape)}")
-    R = torch.empty((B, N + 1, M + 1), device=dev)
-    total = torch.empty(B, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().hmm355_softdtw_f32(nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, float(gamma),
-                                               nat.ptr(R), nat.ptr(total), nat.stream_of(dev)))
-    return R, total
+    R, total = outs = _soft_dtw_outputs(_on(dev), B, N, M)
+    _call(dev, nat.lib().hmm355_softdtw_f32, nat.ptr(dist), nat.ptr(n_len), nat.ptr(m_len), B, N, M, float(gamma),
+          nat.ptr(R), nat.ptr(total))
+    return outs
 
 
 @soft_dtw.register_fake
 def _(dist, gamma, n_len=None, m_len=None):
-    B, N, M = dist.shape
-    return dist.new_empty((B, N + 1, M + 1), dtype=torch.float32), dist.new_empty(B, dtype=torch.float32)
+    return _soft_dtw_outputs(dist.new_empty, *dist.shape)
 
 
 @torch.library.custom_op("hmm355::soft_dtw_grad", mutates_args=())
@@ -968,16 +962,15 @@ def soft_dtw_grad(dist: Tensor, R: Tensor, gamma: float, n_len: Optional[Tensor]
     if tuple(R.shape) != (B, N + 1, M + 1):
         raise ValueError(f"R must be ({B}, {N + 1}, {M + 1}); got {tuple(R.shape)}")
     dev = dist.device
-    E = torch.empty((B, N, M), device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().hmm355_softdtw_grad_f32(nat.ptr(dist), nat.ptr(R), nat.ptr(n_len), nat.ptr(m_len), B, N, M,
-                                                    float(gamma), nat.ptr(E), nat.stream_of(dev)))
+    E = _scores_output(_on(dev), B, N, M)
+    _call(dev, nat.lib().hmm355_softdtw_grad_f32, nat.ptr(dist), nat.ptr(R), nat.ptr(n_len), nat.ptr(m_len), B, N, M,
+          float(gamma), nat.ptr(E))
     return E
 
 
 @soft_dtw_grad.register_fake
 def _(dist, R, gamma, n_len=None, m_len=None):
-    return dist.new_empty(tuple(dist.shape), dtype=torch.float32)
+    return _scores_output(dist.new_empty, *dist.shape)
 
 
 # ------------------------------------------------------------------ CTC lattice
@@ -1006,23 +999,24 @@ def _ctc_args(shape, dev, targets, input_lengths, target_lengths, blank):
     blank = int(blank)
     if not 0 <= blank < C:
         raise ValueError(f"blank must lie in [0, {C}); got {blank}")
-    lens = []
-    for name, t, lo, hi in (("input_lengths", input_lengths, 1, T), ("target_lengths", target_lengths, 0, Lmax)):
-        t = torch.as_tensor(t)
-        if t.numel() != B:
-            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
-        host = t.detach().reshape(B).to("cpu", torch.int64)
-        if int(host.min()) < lo or int(host.max()) > hi:
-            raise ValueError(f"{name} must lie in [{lo}, {hi}]; got {host.tolist()}")
-        lens.append(host.to(torch.int32).to(dev))
+    il = _lengths(input_lengths, "input_lengths", B, 1, T, dev)[1]
+    tl = _lengths(target_lengths, "target_lengths", B, 0, Lmax, dev)[1]
     tg = targets.detach().to(device=dev, dtype=torch.int32)
     if Lmax == 0:
         tg = torch.zeros((B, 1), dtype=torch.int32, device=dev)
     else:
-        used = torch.arange(Lmax, device=dev)[None, :] < lens[1][:, None]
+        used = torch.arange(Lmax, device=dev)[None, :] < tl[:, None]
         if bool((((tg < 0) | (tg >= C)) & used).any()):
             raise ValueError(f"targets hold labels outside [0, {C})")
-    return tg.contiguous(), lens[0], lens[1], blank, Lmax
+    return tg.contiguous(), il, tl, blank, Lmax
+
+
+def _lattice_outputs(mk, B, T, S, alpha, beta, viterbi):
+    """(loglik, alpha, beta, path, score) of a lattice of S positions: ctc's outputs and the first
+    five of forced's."""
+    return (mk(B, dtype=_F32), mk((B, T, S) if alpha else _EMPTY, dtype=_F32),
+            mk((B, T, S) if beta else _EMPTY, dtype=_F32), mk((B, T) if viterbi else _EMPTY, dtype=_I32),
+            mk(B if viterbi else 0, dtype=_F32))
 
 
 @torch.library.custom_op("hmm355::ctc", mutates_args=())
@@ -1045,21 +1039,12 @@ def ctc(log_probs: Tensor, targets: Tensor, input_lengths: Tensor, target_length
     lp = _f32c(log_probs.detach())
     T, B, C = lp.shape
     Lk = tg.shape[1]
-    Sk = 2 * Lk + 1
-    A = torch.empty((B, T, Sk) if alpha else _EMPTY, device=dev)
-    Bt = torch.empty((B, T, Sk) if beta else _EMPTY, device=dev)
-    loglik = torch.empty(B, device=dev)
-    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
-    score = torch.empty(B if viterbi else 0, device=dev)
+    loglik, A, Bt, path, score = _lattice_outputs(_on(dev), B, T, 2 * Lk + 1, alpha, beta, viterbi)
     flags = (CTC_ALPHA if alpha else 0) | (CTC_BETA if beta else 0) | (CTC_VITERBI if viterbi else 0)
     L = nat.lib()
-    ws = _workspace(L.hmm355_ctc_workspace_bytes(B, T, Lk, flags), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_ctc_f32(
-            nat.ptr(lp), nat.ptr(tg), nat.ptr(il), nat.ptr(tl), T, B, C, Lk, blank, flags,
-            nat.ptr(A) if alpha else None, nat.ptr(Bt) if beta else None, nat.ptr(loglik),
-            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
-            nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    _call(dev, L.hmm355_ctc_f32, nat.ptr(lp), nat.ptr(tg), nat.ptr(il), nat.ptr(tl), T, B, C, Lk, blank, flags,
+          _opt(A, alpha), _opt(Bt, beta), nat.ptr(loglik), _opt(path, viterbi), _opt(score, viterbi),
+          ws=L.hmm355_ctc_workspace_bytes(B, T, Lk, flags))
     if Lk != Lmax:  # an empty targets matrix: the lattice is the single blank position
         if alpha:
             A = A[:, :, :1].contiguous()
@@ -1071,14 +1056,12 @@ def ctc(log_probs: Tensor, targets: Tensor, input_lengths: Tensor, target_length
 @ctc.register_fake
 def _(log_probs, targets, input_lengths, target_lengths, blank=0, alpha=False, beta=False, viterbi=False):
     T, B, _ = log_probs.shape
-    S = 2 * targets.shape[1] + 1
-    f32 = torch.float32
-    return (log_probs.new_empty(B, dtype=f32),
-            log_probs.new_empty((B, T, S) if alpha else _EMPTY, dtype=f32),
-            log_probs.new_empty((B, T, S) if beta else _EMPTY, dtype=f32),
-            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
-            log_probs.new_empty(B if viterbi else 0, dtype=f32))
+    return _lattice_outputs(log_probs.new_empty, B, T, 2 * targets.shape[1] + 1, alpha, beta, viterbi)
 
+
+def _ctc_grad_outputs(mk, B, T, C, S, want_gamma):
+    """(grad, gamma)."""
+    return mk((T, B, C), dtype=_F32), mk((B, T, S) if want_gamma else _EMPTY, dtype=_F32)
 
 
 
@@ -1106,12 +1089,9 @@ def ctc_grad(alpha: Tensor, beta: Tensor, loglik: Tensor, targets: Tensor, input
     if Lk != Lmax:  # an empty targets matrix: widen the single blank column to the kernel's Lmax = 1
         pad = alpha.new_full((B, T, 2), float("-inf"))
         alpha, beta = torch.cat([alpha, pad], 2).contiguous(), torch.cat([beta, pad], 2).contiguous()
-    grad = torch.empty((T, B, C), device=dev)
-    gamma = torch.empty((B, T, 2 * Lk + 1) if want_gamma else _EMPTY, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().hmm355_ctc_grad_f32(
-            nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(tg), nat.ptr(il), nat.ptr(tl), T, B, C, Lk, blank,
-            nat.ptr(gamma) if want_gamma else None, nat.ptr(grad), nat.stream_of(dev)))
+    grad, gamma = _ctc_grad_outputs(_on(dev), B, T, C, 2 * Lk + 1, want_gamma)
+    _call(dev, nat.lib().hmm355_ctc_grad_f32, nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(tg), nat.ptr(il),
+          nat.ptr(tl), T, B, C, Lk, blank, _opt(gamma, want_gamma), nat.ptr(grad))
     if want_gamma and Lk != Lmax:
         gamma = gamma[:, :, :1].contiguous()
     return grad, gamma
@@ -1120,8 +1100,7 @@ def ctc_grad(alpha: Tensor, beta: Tensor, loglik: Tensor, targets: Tensor, input
 @ctc_grad.register_fake
 def _(alpha, beta, loglik, targets, input_lengths, target_lengths, num_classes, blank=0, want_gamma=False):
     B, T, S = alpha.shape
-    return (alpha.new_empty((T, B, num_classes), dtype=torch.float32),
-            alpha.new_empty((B, T, S) if want_gamma else _EMPTY, dtype=torch.float32))
+    return _ctc_grad_outputs(alpha.new_empty, B, T, num_classes, S, want_gamma)
 
 
 # ------------------------------------------------------------------ transcript forced alignment
@@ -1157,15 +1136,8 @@ def _forced_args(shape, dev, state_ids, input_lengths, state_lengths, log_stay=N
                              f"C >= {Smax}; got C = {C}")
     if Smax < 1 or Smax > FORCED_MAX_POSITIONS:
         raise ValueError(f"chains of 1 to {FORCED_MAX_POSITIONS} positions are supported; got {Smax}")
-    lens = []
-    for name, t, hi in (("input_lengths", input_lengths, T), ("state_lengths", state_lengths, Smax)):
-        t = torch.as_tensor(t)
-        if t.numel() != B:
-            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
-        host = t.detach().reshape(B).to("cpu", torch.int64)
-        if int(host.min()) < 1 or int(host.max()) > hi:
-            raise ValueError(f"{name} must lie in [1, {hi}]; got {host.tolist()}")
-        lens.append(host.to(torch.int32).to(dev))
+    il = _lengths(input_lengths, "input_lengths", B, 1, T, dev)[1]
+    sl = _lengths(state_lengths, "state_lengths", B, 1, Smax, dev)[1]
     ws = []
     for name, w in weights:
         if w is not None:
@@ -1174,7 +1146,18 @@ def _forced_args(shape, dev, state_ids, input_lengths, state_lengths, log_stay=N
             w = _f32c(w.detach().to(dev))
         ws.append(w)
     ids = None if state_ids is None else state_ids.detach().to(device=dev, dtype=torch.int32).contiguous()
-    return ids, lens[0], lens[1], ws[0], ws[1], ws[2], Smax
+    return ids, il, sl, ws[0], ws[1], ws[2], Smax
+
+
+def _forced_outputs(mk, B, T, S, alpha, beta, viterbi):
+    """(loglik, alpha, beta, path, score, durations)."""
+    return (*_lattice_outputs(mk, B, T, S, alpha, beta, viterbi), mk((B, S) if viterbi else _EMPTY, dtype=_I32))
+
+
+def _forced_grad_outputs(mk, B, T, C, S, want_gamma, want_grad, want_stay, want_next, want_skip):
+    """(gamma, grad_log_probs, grad_stay, grad_next, grad_skip)."""
+    return tuple(mk(shape if want else _EMPTY, dtype=_F32) for want, shape in (
+        (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S))))
 
 
 @torch.library.custom_op("hmm355::forced", mutates_args=())
@@ -1200,22 +1183,13 @@ def forced(log_probs: Tensor, state_ids: Optional[Tensor], input_lengths: Tensor
                                               log_stay, log_next, log_skip)
     lp = _f32c(log_probs.detach())
     B, T, C = lp.shape
-    A = torch.empty((B, T, S) if alpha else _EMPTY, device=dev)
-    Bt = torch.empty((B, T, S) if beta else _EMPTY, device=dev)
-    loglik = torch.empty(B, device=dev)
-    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
-    score = torch.empty(B if viterbi else 0, device=dev)
-    dur = torch.empty((B, S) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    loglik, A, Bt, path, score, dur = outs = _forced_outputs(_on(dev), B, T, S, alpha, beta, viterbi)
     flags = (FORCED_ALPHA if alpha else 0) | (FORCED_BETA if beta else 0) | (FORCED_VITERBI if viterbi else 0)
     L = nat.lib()
-    wsp = _workspace(L.hmm355_forced_workspace_bytes(B, T, S, flags), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_forced_f32(
-            nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(ws), nat.ptr(wn), nat.ptr(wk), B, T, C, S,
-            flags, nat.ptr(A) if alpha else None, nat.ptr(Bt) if beta else None, nat.ptr(loglik),
-            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
-            nat.ptr(dur) if viterbi else None, nat.ptr(wsp), wsp.numel(), nat.stream_of(dev)))
-    return loglik, A, Bt, path, score, dur
+    _call(dev, L.hmm355_forced_f32, nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(ws), nat.ptr(wn),
+          nat.ptr(wk), B, T, C, S, flags, _opt(A, alpha), _opt(Bt, beta), nat.ptr(loglik), _opt(path, viterbi),
+          _opt(score, viterbi), _opt(dur, viterbi), ws=L.hmm355_forced_workspace_bytes(B, T, S, flags))
+    return outs
 
 
 def _forced_width(log_probs, state_ids, log_stay, log_next, log_skip):
@@ -1230,13 +1204,7 @@ def _(log_probs, state_ids, input_lengths, state_lengths, log_stay=None, log_nex
       beta=False, viterbi=False):
     B, T, _ = log_probs.shape
     S = _forced_width(log_probs, state_ids, log_stay, log_next, log_skip)
-    f32 = torch.float32
-    return (log_probs.new_empty(B, dtype=f32),
-            log_probs.new_empty((B, T, S) if alpha else _EMPTY, dtype=f32),
-            log_probs.new_empty((B, T, S) if beta else _EMPTY, dtype=f32),
-            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
-            log_probs.new_empty(B if viterbi else 0, dtype=f32),
-            log_probs.new_empty((B, S) if viterbi else _EMPTY, dtype=torch.int32))
+    return _forced_outputs(log_probs.new_empty, B, T, S, alpha, beta, viterbi)
 
 
 @torch.library.custom_op("hmm355::forced_grad", mutates_args=())
@@ -1269,29 +1237,24 @@ def forced_grad(alpha: Tensor, beta: Tensor, loglik: Tensor, log_probs: Tensor, 
     if Sk != S:
         raise ValueError(f"alpha has {S} positions; the chain arguments describe {Sk}")
     alpha, beta, loglik = _f32c(alpha), _f32c(beta), _f32c(loglik)
-    out = [torch.empty(shape if want else _EMPTY, device=dev) for want, shape in (
-        (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S)))]
     wants = (want_gamma, want_grad, want_stay, want_next, want_skip)
+    out = _forced_grad_outputs(_on(dev), B, T, C, S, *wants)
     L = nat.lib()
-    trans = want_stay or want_next or want_skip     # their per-tile sums live in a workspace
-    wsp = _workspace(L.hmm355_forced_workspace_bytes(B, T, S, nat.FORCED_GRAD), dev) if trans else None
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_forced_grad_f32(
-            nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(ids), nat.ptr(il), nat.ptr(sl),
-            nat.ptr(ws), nat.ptr(wn), nat.ptr(wk), B, T, C, S,
-            *[nat.ptr(o) if w else None for o, w in zip(out, wants)], nat.ptr(wsp), wsp.numel() if trans else 0,
-            nat.stream_of(dev)))
-    return tuple(out)
+    args = (nat.ptr(alpha), nat.ptr(beta), nat.ptr(loglik), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(ws),
+            nat.ptr(wn), nat.ptr(wk), B, T, C, S, *[_opt(o, w) for o, w in zip(out, wants)])
+    if want_stay or want_next or want_skip:     # their per-tile sums live in a workspace
+        _call(dev, L.hmm355_forced_grad_f32, *args, ws=L.hmm355_forced_workspace_bytes(B, T, S, nat.FORCED_GRAD))
+    else:
+        _call(dev, L.hmm355_forced_grad_f32, *args, None, 0)
+    return out
 
 
 @forced_grad.register_fake
 def _(alpha, beta, loglik, log_probs, state_ids, input_lengths, state_lengths, log_stay=None, log_next=None,
       log_skip=None, want_gamma=False, want_grad=True, want_stay=False, want_next=False, want_skip=False):
     B, T, S = alpha.shape
-    C = log_probs.shape[2]
-    f32 = torch.float32
-    return tuple(alpha.new_empty(shape if want else _EMPTY, dtype=f32) for want, shape in (
-        (want_gamma, (B, T, S)), (want_grad, (B, T, C)), (want_stay, (B, S)), (want_next, (B, S)), (want_skip, (B, S))))
+    return _forced_grad_outputs(alpha.new_empty, B, T, log_probs.shape[2], S, want_gamma, want_grad, want_stay,
+                                want_next, want_skip)
 
 
 # ------------------------------------------------------------------ explicit-duration forced alignment
@@ -1340,19 +1303,24 @@ def _durforced_args(log_probs, dev, state_ids, input_lengths, state_lengths, dur
         nat.check(nat.lib().hmm355_durforced_f32(None, None, None, None, None, B, T, C, Lmax, Dmax, 0, None, None,
                                                  None, None, None, None, None, None, None, None, None, 0, None))
         raise ValueError(f"dur_lp of {Lmax} positions x {Dmax} durations is outside the supported sizes")
-    lens = []
-    for name, t, hi in (("input_lengths", input_lengths, T), ("state_lengths", state_lengths, Lmax)):
-        t = torch.as_tensor(t)
-        if t.numel() != B:
-            raise ValueError(f"{name} must hold one length per sequence ({B}); got {tuple(t.shape)}")
-        if t.dtype.is_floating_point or t.dtype == torch.bool:
-            raise ValueError(f"{name} must hold integers; got {t.dtype}")
-        host = t.detach().reshape(B).to("cpu", torch.int64)
-        if int(host.min()) < 1 or int(host.max()) > hi:
-            raise ValueError(f"{name} must lie in [1, {hi}]; got {host.tolist()}")
-        lens.append(host.to(torch.int32).to(dev))
+    il = _lengths(input_lengths, "input_lengths", B, 1, T, dev, integers="last")[1]
+    sl = _lengths(state_lengths, "state_lengths", B, 1, Lmax, dev, integers="last")[1]
     ids = None if state_ids is None else state_ids.detach().to(device=dev, dtype=torch.int32).contiguous()
-    return ids, lens[0], lens[1], _f32c(dur_lp.detach().to(dev)), Lmax, Dmax
+    return ids, il, sl, _f32c(dur_lp.detach().to(dev)), Lmax, Dmax
+
+
+def _durforced_outputs(mk, B, T, Lm, tables, viterbi):
+    """(loglik, begin, F, Bend, Bbeg, frame_shift, loglik_shifted, path, score, durations)."""
+    return (mk(B, dtype=_F32), *[mk((B, T, Lm) if tables else _EMPTY, dtype=_F32) for _ in _DURFORCED_TABLES],
+            mk((B, T) if tables else _EMPTY, dtype=_F32), mk(B if tables else 0, dtype=_F32),
+            mk((B, T) if viterbi else _EMPTY, dtype=_I32), mk(B if viterbi else 0, dtype=_F32),
+            mk((B, Lm) if viterbi else _EMPTY, dtype=_I32))
+
+
+def _durforced_grad_outputs(mk, B, T, C, Lm, Dm, want_gamma, want_grad, want_dur):
+    """(gamma, grad_log_probs, grad_dur_lp)."""
+    return tuple(mk(shape if want else _EMPTY, dtype=_F32) for want, shape in (
+        (want_gamma, (B, T, Lm)), (want_grad, (B, T, C)), (want_dur, (B, Lm, Dm))))
 
 
 @torch.library.custom_op("hmm355::durforced", mutates_args=())
@@ -1375,37 +1343,19 @@ def durforced(log_probs: Tensor, state_ids: Optional[Tensor], input_lengths: Ten
     ids, il, sl, du, Lm, Dm = _durforced_args(log_probs, dev, state_ids, input_lengths, state_lengths, dur_lp)
     lp = _f32c(log_probs.detach())
     B, T, C = lp.shape
-    tabs = [torch.empty((B, T, Lm) if tables else _EMPTY, device=dev) for _ in _DURFORCED_TABLES]
-    shift = torch.empty((B, T) if tables else _EMPTY, device=dev)
-    lls = torch.empty(B if tables else 0, device=dev)
-    loglik = torch.empty(B, device=dev)
-    path = torch.empty((B, T) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
-    score = torch.empty(B if viterbi else 0, device=dev)
-    dur = torch.empty((B, Lm) if viterbi else _EMPTY, dtype=torch.int32, device=dev)
+    loglik, *tabs, path, score, dur = outs = _durforced_outputs(_on(dev), B, T, Lm, tables, viterbi)
     flags = (nat.DURFORCED_TABLES if tables else 0) | (nat.DURFORCED_VITERBI if viterbi else 0)
     L = nat.lib()
-    wsp = _workspace(L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, flags), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_durforced_f32(
-            nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du), B, T, C, Lm, Dm, flags,
-            *[nat.ptr(t) if tables else None for t in (*tabs, shift, lls)], nat.ptr(loglik),
-            nat.ptr(path) if viterbi else None, nat.ptr(score) if viterbi else None,
-            nat.ptr(dur) if viterbi else None, nat.ptr(wsp), wsp.numel(), nat.stream_of(dev)))
-    return (loglik, *tabs, shift, lls, path, score, dur)
+    _call(dev, L.hmm355_durforced_f32, nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du), B, T, C, Lm,
+          Dm, flags, *[_opt(t, tables) for t in tabs], nat.ptr(loglik), _opt(path, viterbi), _opt(score, viterbi),
+          _opt(dur, viterbi), ws=L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, flags))
+    return outs
 
 
 @durforced.register_fake
 def _(log_probs, state_ids, input_lengths, state_lengths, dur_lp, *, tables=False, viterbi=False):
     B, T, _ = log_probs.shape
-    Lm = dur_lp.shape[1]
-    f32 = torch.float32
-    tab = lambda: log_probs.new_empty((B, T, Lm) if tables else _EMPTY, dtype=f32)
-    return (log_probs.new_empty(B, dtype=f32), tab(), tab(), tab(), tab(),
-            log_probs.new_empty((B, T) if tables else _EMPTY, dtype=f32),
-            log_probs.new_empty(B if tables else 0, dtype=f32),
-            log_probs.new_empty((B, T) if viterbi else _EMPTY, dtype=torch.int32),
-            log_probs.new_empty(B if viterbi else 0, dtype=f32),
-            log_probs.new_empty((B, Lm) if viterbi else _EMPTY, dtype=torch.int32))
+    return _durforced_outputs(log_probs.new_empty, B, T, dur_lp.shape[1], tables, viterbi)
 
 
 @torch.library.custom_op("hmm355::durforced_grad", mutates_args=())
@@ -1434,29 +1384,33 @@ def durforced_grad(begin: Tensor, F: Tensor, Bend: Tensor, Bbeg: Tensor, frame_s
     lp = _f32c(log_probs.detach())
     tabs = [_f32c(t) for t in (begin, F, Bend, Bbeg, frame_shift, loglik_shifted)]
     wants = (want_gamma, want_grad, want_dur)
-    out = [torch.empty(shape if want else _EMPTY, device=dev)
-           for want, shape in zip(wants, ((B, T, Lm), (B, T, C), (B, Lm, Dm)))]
+    out = _durforced_grad_outputs(_on(dev), B, T, C, Lm, Dm, *wants)
     L = nat.lib()
-    need_ws = want_dur or (want_grad and not want_gamma)
-    wsp = _workspace(L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, nat.DURFORCED_GRAD), dev) if need_ws else None
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_durforced_grad_f32(
-            *[nat.ptr(t) for t in tabs], nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du),
-            B, T, C, Lm, Dm, *[nat.ptr(o) if w else None for o, w in zip(out, wants)], nat.ptr(wsp),
-            wsp.numel() if need_ws else 0, nat.stream_of(dev)))
-    return tuple(out)
+    args = (*[nat.ptr(t) for t in tabs], nat.ptr(lp), nat.ptr(ids), nat.ptr(il), nat.ptr(sl), nat.ptr(du), B, T, C,
+            Lm, Dm, *[_opt(o, w) for o, w in zip(out, wants)])
+    if want_dur or (want_grad and not want_gamma):
+        _call(dev, L.hmm355_durforced_grad_f32, *args,
+              ws=L.hmm355_durforced_workspace_bytes(B, T, Lm, Dm, nat.DURFORCED_GRAD))
+    else:
+        _call(dev, L.hmm355_durforced_grad_f32, *args, None, 0)
+    return out
 
 
 @durforced_grad.register_fake
 def _(begin, F, Bend, Bbeg, frame_shift, loglik_shifted, log_probs, state_ids, input_lengths, state_lengths, dur_lp, *,
       want_gamma=False, want_grad=True, want_dur=False):
     B, T, C = log_probs.shape
-    Lm, Dm = dur_lp.shape[1], dur_lp.shape[2]
-    return tuple(log_probs.new_empty(shape if want else _EMPTY, dtype=torch.float32) for want, shape in (
-        (want_gamma, (B, T, Lm)), (want_grad, (B, T, C)), (want_dur, (B, Lm, Dm))))
+    return _durforced_grad_outputs(log_probs.new_empty, B, T, C, dur_lp.shape[1], dur_lp.shape[2], want_gamma,
+                                   want_grad, want_dur)
 
 
 # ------------------------------------------------------------------ duration-constrained Viterbi
+def _dchmm_outputs(mk, B, T, S, want_trellis):
+    """(states, final_score, log_delta, durations)."""
+    trellis = (B, T, S) if want_trellis else _EMPTY
+    return mk((B, T), dtype=_I64), mk(B, dtype=_F32), mk(trellis, dtype=_F32), mk(trellis, dtype=_I32)
+
+
 @torch.library.custom_op("hmm355::duration_constrained_viterbi", mutates_args=())
 def duration_constrained_viterbi(emission_log_probs: Tensor, log_transitions: Tensor, min_duration: int,
                                  max_duration: int, penalty_weight: float = 0.1, per_sequence: bool = False,
@@ -1488,28 +1442,18 @@ def duration_constrained_viterbi(emission_log_probs: Tensor, log_transitions: Te
             "decodes each sequence with its own penalties at any B")
     dev = emission_log_probs.device
     e, lT = _f32c(emission_log_probs.detach()), _f32c(log_transitions.detach())
-    states = torch.empty((B, T), dtype=torch.int64, device=dev)
-    score = torch.empty(B, device=dev)
-    delta = torch.empty((B, T, S) if want_trellis else _EMPTY, device=dev)
-    dur = torch.empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.int32, device=dev)
+    states, score, delta, dur = outs = _dchmm_outputs(_on(dev), B, T, S, want_trellis)
     L = nat.lib()
-    ws = _workspace(L.hmm355_dchmm_workspace_bytes(B, T, S), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_dchmm_viterbi_f32(
-            nat.ptr(e), nat.ptr(lT), B, T, S, group, int(min_duration), int(max_duration), float(penalty_weight),
-            nat.ptr(states), nat.ptr(score), nat.ptr(delta) if want_trellis else None,
-            nat.ptr(dur) if want_trellis else None, nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
-    return states, score, delta, dur
+    _call(dev, L.hmm355_dchmm_viterbi_f32, nat.ptr(e), nat.ptr(lT), B, T, S, group, int(min_duration),
+          int(max_duration), float(penalty_weight), nat.ptr(states), nat.ptr(score), _opt(delta, want_trellis),
+          _opt(dur, want_trellis), ws=L.hmm355_dchmm_workspace_bytes(B, T, S))
+    return outs
 
 
 @duration_constrained_viterbi.register_fake
 def _(emission_log_probs, log_transitions, min_duration, max_duration, penalty_weight=0.1, per_sequence=False,
       want_trellis=False):
-    B, T, S = emission_log_probs.shape
-    return (emission_log_probs.new_empty((B, T), dtype=torch.int64),
-            emission_log_probs.new_empty(B, dtype=torch.float32),
-            emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.float32),
-            emission_log_probs.new_empty((B, T, S) if want_trellis else _EMPTY, dtype=torch.int32))
+    return _dchmm_outputs(emission_log_probs.new_empty, *emission_log_probs.shape, want_trellis)
 
 
 # ------------------------------------------------------------------ posterior path sampling
@@ -1523,6 +1467,11 @@ def _row_stride(x: Tensor) -> Optional[int]:
     if ld < N or (T > 1 and B > 1 and x.stride(0) != T * ld):
         return None
     return ld
+
+
+def _ffbs_output(mk, B, K, T):
+    """states."""
+    return mk((B, K, T), dtype=_I64)
 
 
 @torch.library.custom_op("hmm355::ffbs", mutates_args=())
@@ -1555,22 +1504,19 @@ def ffbs(fwd: Tensor, log_P: Tensor, uniforms: Tensor, lengths: Optional[Tensor]
         fwd = fwd.contiguous()
         ld = N
     log_P, uniforms = _f32c(log_P.detach()), _f32c(uniforms.detach())
-    states = torch.empty((B, K, T), dtype=torch.int64, device=dev)
+    states = _ffbs_output(_on(dev), B, K, T)
     if B == 0 or T == 0:
         return states
     lens = None if host is None else host.to(torch.int32).to(dev)
     L = nat.lib()
-    ws = _workspace(L.hmm355_ffbs_workspace_bytes(N), dev)
-    with torch.cuda.device(dev):
-        nat.check(L.hmm355_ffbs_f32(nat.ptr(fwd), int(ld), nat.ptr(log_P), nat.ptr(lens), nat.ptr(uniforms), B, T, N, K,
-                                    nat.ptr(states), nat.ptr(ws), ws.numel(), nat.stream_of(dev)))
+    _call(dev, L.hmm355_ffbs_f32, nat.ptr(fwd), int(ld), nat.ptr(log_P), nat.ptr(lens), nat.ptr(uniforms), B, T, N, K,
+          nat.ptr(states), ws=L.hmm355_ffbs_workspace_bytes(N))
     return states
 
 
 @ffbs.register_fake
 def _(fwd, log_P, uniforms, lengths=None):
-    B, T, _ = fwd.shape
-    return fwd.new_empty((B, uniforms.shape[1], T), dtype=torch.int64)
+    return _ffbs_output(fwd.new_empty, fwd.shape[0], uniforms.shape[1], fwd.shape[1])
 
 
 def posterior_sample(obs: Tensor, log_P: Tensor, log_p0: Tensor, obs_mode: int, num_samples: int, *,
