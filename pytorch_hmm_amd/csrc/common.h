@@ -53,7 +53,7 @@ constexpr int kFAbl = HMM355_FABL;
 
 // The bits of HMM355_ABL: one meaning each, tested as `kAbl & abl::kName`.  Every one of them
 // gives wrong results: timing only.  The values 1, 2, 4, 8, 16 (tools/ablate.py) and 1, 1 << 20,
-// 1 << 21 (tools/ablate_hsmm.py) are passed by number: keep them.  Free: bits 8..13 and 27.
+// 1 << 21 (tools/ablate_hsmm.py) are passed by number: keep them.  Free: bits 8..13.
 namespace abl {
 constexpr int kNoStepBarrier = 1;           // step_barrier(): rec_run_dpp / rec_run_rb, hsmm.hip, semimarkov.hip
 constexpr int kDppNoProducts = 2;           // rec_run_dpp (NP = 256 only): sums / maxima of the inputs, no matrix
@@ -76,6 +76,7 @@ constexpr int kBandNoReduce = 1 << 23;      // band_chain: lane 0's value instea
 constexpr int kBandReducePrev = 1 << 24;    // band_chain, Viterbi: the previous step's reduction (off the chain)
 constexpr int kPairNoScale = 1 << 25;       // fbpair.h: posteriors without the 1/s scaling
 constexpr int kPairNoTasks = 1 << 26;       // fbpair.h: no row tasks
+constexpr int kBandEmisReg = 1 << 27;       // band_chain: the block's first emission row in every step, no per-step LDS read
 constexpr int kPairNoPostStores = 1 << 28;  // fbpair.h: no posterior stores
 constexpr int kPairNoStores = 1 << 29;      // fbpair.h: no output, scratch or posterior stores
 constexpr int kPairPlainStores = 1 << 30;   // fbpair.h: default cache policy instead of non-temporal

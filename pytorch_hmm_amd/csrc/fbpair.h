@@ -80,16 +80,18 @@ __device__ __forceinline__ void buf_load(__amdgpu_buffer_rsrc_t r, int off, floa
 
 template <int NP, int KIND>
 __device__ __forceinline__ void band_chain_dispatch(const RecArgs& a, float* lds, int b, int code) {
+  // EA = 1: the pair kernel's chains read their emission row one step ahead (recur.h emis_ahead:
+  // the distance of two was measured on the chain kernels alone; this kernel is at its register cap)
   switch (code) {
-    case 2: band_chain<NP, KIND, 2>(a, lds, b, a.band); break;
-    case 4: band_chain<NP, KIND, 4>(a, lds, b, a.band); break;
-    case 8: band_chain<NP, KIND, 8>(a, lds, b, a.band); break;
-    case 16 * 1 + 0 + 2: band_chain<NP, KIND, 2, 0, 1>(a, lds, b, a.band); break;
-    case 16 * 2 - 1 + 2: band_chain<NP, KIND, 2, -1, 2>(a, lds, b, a.band); break;
-    case 16 * 2 + 0 + 2: band_chain<NP, KIND, 2, 0, 2>(a, lds, b, a.band); break;
-    case 16 * 3 - 2 + 2: band_chain<NP, KIND, 2, -2, 3>(a, lds, b, a.band); break;
-    case 16 * 3 - 1 + 2: band_chain<NP, KIND, 2, -1, 3>(a, lds, b, a.band); break;
-    default: band_chain<NP, KIND, 2, 0, 3>(a, lds, b, a.band); break;  // 16 * 3 + 0 + 2
+    case 2: band_chain<NP, KIND, 2, 0, 0, 1>(a, lds, b, a.band); break;
+    case 4: band_chain<NP, KIND, 4, 0, 0, 1>(a, lds, b, a.band); break;
+    case 8: band_chain<NP, KIND, 8, 0, 0, 1>(a, lds, b, a.band); break;
+    case 16 * 1 + 0 + 2: band_chain<NP, KIND, 2, 0, 1, 1>(a, lds, b, a.band); break;
+    case 16 * 2 - 1 + 2: band_chain<NP, KIND, 2, -1, 2, 1>(a, lds, b, a.band); break;
+    case 16 * 2 + 0 + 2: band_chain<NP, KIND, 2, 0, 2, 1>(a, lds, b, a.band); break;
+    case 16 * 3 - 2 + 2: band_chain<NP, KIND, 2, -2, 3, 1>(a, lds, b, a.band); break;
+    case 16 * 3 - 1 + 2: band_chain<NP, KIND, 2, -1, 3, 1>(a, lds, b, a.band); break;
+    default: band_chain<NP, KIND, 2, 0, 3, 1>(a, lds, b, a.band); break;  // 16 * 3 + 0 + 2
   }
 }
 

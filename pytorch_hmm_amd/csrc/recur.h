@@ -36,6 +36,32 @@ namespace hmm355 {
 enum RecKind : int { kFbAlpha = 0, kFbBeta = 1, kVit = 2 };
 typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned int))));  // (as fbpair.h)
 
+// How many steps ahead the banded chain wave (band_chain) reads a step's staged emission row
+// inside an unrolled 16-step block, by chain: 1 or 2.  Two for beta and Viterbi, whose reduction
+// is filled (wave_red_fill): the wait for a row read two steps ahead stands in gap kEmisWaitGap
+// of the step in between, in the place of a wait state, and the step loses the issue slot the
+// s_waitcnt took ahead of the row's first use.  alpha leaves its placing to the compiler and
+// measured slower at two.  The macros are for diagnostic builds.
+#ifndef HMM355_EMIS_AHEAD_ALPHA
+#define HMM355_EMIS_AHEAD_ALPHA 1
+#endif
+#ifndef HMM355_EMIS_AHEAD_BETA
+#define HMM355_EMIS_AHEAD_BETA 2
+#endif
+#ifndef HMM355_EMIS_AHEAD_VIT
+#define HMM355_EMIS_AHEAD_VIT 2
+#endif
+// the gap of the filled reduction (wave_red_fill) that holds the wait for a row read two steps
+// ahead: 4, ahead of row_bcast:15, which the register windows of up to two states a lane (NP <= 128)
+// leave empty (fill_cnt); where the step's own units fill it the wait costs there what it saved
+#ifndef HMM355_EMIS_WAIT_GAP
+#define HMM355_EMIS_WAIT_GAP 4
+#endif
+constexpr int kEmisWaitGap = HMM355_EMIS_WAIT_GAP;
+constexpr int emis_ahead(int kind) {
+  return kind == kFbAlpha ? HMM355_EMIS_AHEAD_ALPHA : kind == kFbBeta ? HMM355_EMIS_AHEAD_BETA : HMM355_EMIS_AHEAD_VIT;
+}
+
 // diagnostic builds (HMM355_STAMP=1): per wave [gather, compute, write-wait, barrier, steps,
 // total cycles, memtime, memrealtime] summed over the steps (tools/stamps.py)
 constexpr int kStampWaves = 512 * 16;
@@ -1220,7 +1246,7 @@ constexpr int win_shift_term(int m, int NB, int NWIN, int TD0) {
 // kernel, fbpair.h): the whole recursion of one sequence in one wave, one lds_barrier per
 // 16-step block and one after the last row, matching the helpers' barriers.  `lds` is the
 // chain's own RC<NP> layout.
-template <int NP, int KIND, int WP, int TD0 = 0, int TW = 0>
+template <int NP, int KIND, int WP, int TD0 = 0, int TW = 0, int EA = emis_ahead(KIND)>
 __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, const BandDesc* __restrict__ d) {
   using C = RC<NP>;
   constexpr int NB = C::NBLK;
@@ -1239,7 +1265,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // they become v_fmac only afterwards), so their shifts stay a v_mov_b32_dpp each (NP = 128
   // listings).  A wave issues one instruction per ~4 cycles, so the step is
   // written for instruction count: 16-step blocks fully unrolled (no scalar address math),
-  // the emission read one step ahead, the block's normalisers collected by v_writelane and
+  // the emission read EA steps ahead (emis_ahead), the block's normalisers collected by v_writelane and
   // stored once per block.
   constexpr int WW = TW > 0 ? TW : WP;  // window slots per state
   int lo[NB];
@@ -1265,6 +1291,12 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     else if constexpr (NB == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; }
     else { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
   };
+  // one empty asm over a whole register set: the compiler's wait for its read stands ahead of it
+  auto pin_all = [&](float(&v)[NB]) {
+    if constexpr (NB == 1) asm volatile("" : "+v"(v[0]));
+    else if constexpr (NB == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+    else asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+  };
   auto st = [&](float* p, const float(&v)[NB]) {
     if constexpr (NB == 1) p[0] = v[0];
     else if constexpr (NB == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
@@ -1279,7 +1311,9 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   }
   float* ybuf = lds + C::OFF_PART;  // beta's LDS window source [2][NP] (LDS-window mode)
   constexpr int EL = KIND == kFbBeta ? 1 : 0;
-  float en[NB];  // the next step's emission (alpha / Viterbi e_q, beta e_{q-1})
+  // the coming steps' emissions (alpha / Viterbi e_q, beta e_{q-1}), read EA steps ahead inside
+  // an unrolled block: step jj takes slot jj % EA and refills it with the row of step jj + EA
+  float en[EA][NB];
   // the step sum's pinned form (prod_sum): which product of the first pair is fused.  What the
   // compiler chose per instantiation before the form was written out: the first one for four
   // states per lane and for two with a Toeplitz window of offsets 0 .. +1 or 0 .. +2, else the
@@ -1335,8 +1369,14 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // RL (beta): the step's input row came across a loop's back edge -- every step of the rolled
   // loop (the partial blocks) and step 0 of an unrolled block -- where the compiler had fused
   // the first product whatever the window
-  auto step = [&](int q, int jj, bool last_in_block, auto UA, auto FP, auto RL, float* row, const float* enext, float& blk,
-                  auto wlane) {
+  // ES: the slot of `en` the step takes its emission from and reads enext into (no_read: nothing
+  // left to read in this block)
+  // PW (EA = 2, the chains whose reduction is filled): the wait for the NEXT step's row, read a
+  // step ago, stands in gap kEmisWaitGap of this step's reduction, where it takes the place of a
+  // wait state the level behind it needs anyway; left to the compiler it stands ahead of the
+  // row's first use, an issue slot of its own in every step
+  auto step = [&](int q, int jj, bool no_read, auto UA, auto FP, auto RL, auto ES, auto PW, float* row, const float* enext,
+                  float& blk, auto wlane) {
     constexpr bool FILLED = KIND != kFbAlpha;
     constexpr bool LW = TW == 0;                                     // LDS-window mode
     constexpr bool WFILL = !(KIND == kFbAlpha && !decltype(UA)::value);  // the window terms are fillers
@@ -1349,7 +1389,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     constexpr int O_T = O_EN + 1, O_SH = O_T + (SPLIT ? NB : 0), NU = O_T + (WFILL ? NWIN + NSH : 0);
     float eo[NB];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) eo[j] = en[j];
+    for (int j = 0; j < NB; ++j) eo[j] = en[decltype(ES)::value][j];
     float acc[NB], src[NB], wl[NB][WW], tv[NB][WW], sh[5 * NB];
     float cs = 0.f, scale = 1.f;
     const float* wsrc = KIND == kFbBeta ? ybuf + ((q - 1) & 1) * NP : row;
@@ -1394,7 +1434,10 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       } else if constexpr (i < O_EN) {
         st(row + NB * l, y);
       } else if constexpr (i == O_EN) {
-        if (!last_in_block) ld(enext, en);
+        // (diagnostic timing bit, wrong results: kBandEmisReg no read, the block's first row stays)
+        if constexpr (!(kAbl & abl::kBandEmisReg)) {
+          if (!no_read) ld(enext, en[decltype(ES)::value]);
+        }
       } else if constexpr (i < O_SH) {
         term(i - O_T);  // (SPLIT) the first terms
       } else if constexpr (i < O_SH + NSH) {
@@ -1403,7 +1446,11 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         term(i - O_T - NSH);
       }
     };
-    auto fill = [&](auto G) { static_for<fill_lo(decltype(G)::value, NU), fill_lo(decltype(G)::value + 1, NU)>(unit); };
+    auto fill = [&](auto G) {
+      static_for<fill_lo(decltype(G)::value, NU), fill_lo(decltype(G)::value + 1, NU)>(unit);
+      if constexpr (decltype(PW)::value && decltype(G)::value == kEmisWaitGap && !(kAbl & abl::kBandEmisReg))
+        pin_all(en[EA - 1 - decltype(ES)::value]);
+    };
     // (diagnostic timing bits, wrong results: kBandNoReduce no reduction, kBandReducePrev the
     // reduction of the previous step's values, off the step's dependency chain)
     auto reduce = [&](auto MAXOP, float t) -> float {
@@ -1501,18 +1548,24 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     for (int kb = 0; kb < nblocks; ++kb) {
       const int q0 = kb * 16 < 1 ? 1 : kb * 16;
       const int q1 = (kb + 1) * 16 < T ? (kb + 1) * 16 : T;
-      if (q0 < q1) ld(erow(q0 - EL), en);
+      if (q0 < q1) ld(erow(q0 - EL), en[0]);
       // step jj of this block writes row 16kb + jj - 1: slot (16kb & 63) + jj - 1 for jj >= 1
       // (no wrap inside a block), slot (16kb - 1) & 63 for jj = 0; it loads the emission row
-      // of step 16kb + jj + 1 - EL, slot (kb % 3) * 16 + jj + 1 - EL of the staging ring
+      // of step 16kb + jj + EA - EL (the rolled loop: + 1), slot (kb % 3) * 16 + jj + EA - EL of
+      // the staging ring.  The rows of steps 1 .. EA - 1 are read here, behind the barrier that
+      // staged this block: no read crosses a block's edge (beta's step 0 takes its row from the
+      // previous block's slot, staged a block ago, and it is read here too)
       float* rbase = lds + C::OFF_RING + ((16 * kb) & (C::RING - 1)) * NP;
       float* rwrap = lds + C::OFF_RING + ((16 * kb - 1) & (C::RING - 1)) * NP;
       const float* ebase = lds + C::OFF_EMIS + ((kb % 3) * 16 + 1 - EL) * NP + NB * l;
       float blk = 0.f;
       if (q0 == kb * 16 && q1 == kb * 16 + 16) {
+        static_for<1, EA>([&](auto K) { ld(ebase + (decltype(K)::value - 1) * NP, en[decltype(K)::value]); });
         static_for<0, 16>([&](auto JJ) {
           constexpr int jj = decltype(JJ)::value;
-          step(kb * 16 + jj, jj, jj == 15, UA, std::bool_constant<(jj > 0)>{}, std::bool_constant<(jj == 0)>{}, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
+          step(kb * 16 + jj, jj, jj + EA > 15, UA, std::bool_constant<(jj > 0)>{}, std::bool_constant<(jj == 0)>{},
+               std::integral_constant<int, jj % EA>{}, std::bool_constant<(EA == 2 && KIND != kFbAlpha && jj < 15)>{},
+               jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + (jj + EA - 1) * NP, blk,
                [](float& d, float v) { writelane_c<jj>(d, v); });
         });
         // the block's normalisers / floor maxima: lane jj -> row 16kb + jj - 1 (entry 0 of its
@@ -1525,7 +1578,8 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         for (int q = q0; q < q1; ++q) {
           const int jj = q - kb * 16;
           float* sc = lds + C::OFF_SC + 64 * ((q - 1) & (C::RING - 1));
-          step(q, jj, q + 1 == q1, UA, std::false_type{}, std::true_type{}, jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
+          step(q, jj, q + 1 == q1, UA, std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, std::false_type{},
+               jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, blk,
                [sc](float&, float v) { *sc = v; });
         }
       }

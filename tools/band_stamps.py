@@ -1,6 +1,6 @@
 """Diagnostic: cycles and shader clock of the banded chain waves (HMM355_STAMP=1 build,
 recur.h band_chain), each op alone and both ops side by side on two streams.
-Build here:  python tools/band_stamps.py build [items]     Run on the GPU box: python tools/band_stamps.py [f]
+Build here:  [STAMP_LIB=path] [STAMP_DEFINES="A=1 B=2"] python tools/band_stamps.py build [items]     Run on the GPU box: [STAMP_LIB=path] python tools/band_stamps.py [f]
 (f: the work beside the chains on; items: also the staging helpers' work by item and the psi waves).  Per chain: cycles per step, cycles per step at the block
 barriers (waiting for the helpers), and the clock (s_memtime cycles / s_memrealtime at 100 MHz)."""
 import ctypes
@@ -15,7 +15,9 @@ if sys.argv[1:2] == ["build"]:
     sys.path.insert(0, os.path.dirname(HERE))
     from pytorch_hmm_amd import build_native as bn
     level = 2 if sys.argv[2:] == ["items"] else 1
-    print(bn.build(force=True, defines=[f"HMM355_STAMP={level}"], out=LIB, sources=bn.RECURSION_SOURCES))
+    # STAMP_DEFINES: further defines, e.g. "HMM355_EMIS_AHEAD_BETA=2" or "HMM355_ABL=134217728" (wrong results)
+    extra = os.environ.get("STAMP_DEFINES", "").split()
+    print(bn.build(force=True, defines=[f"HMM355_STAMP={level}", *extra], out=LIB, sources=bn.RECURSION_SOURCES))
     sys.exit(0)
 import numpy as np
 import torch
