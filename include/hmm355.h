@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]; emission statistics hmm355_gmm_stats_f32 C [1, 256], S*C <= 65536) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]; emission statistics hmm355_gmm_stats_f32 C [1, 256], S*C <= 65536; N-best Viterbi hmm355_viterbi_nbest_f32 N [1, 256], K <= 16) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -332,6 +332,44 @@ size_t hmm355_ffbs_workspace_bytes(int N);
 int hmm355_ffbs_f32(const float* fwd, int ld, const float* log_P, const int* lengths /* (B) or NULL */,
                     const float* uniforms /* (B,K,T) */, int B, int T, int N, int K,
                     int64_t* states /* (B,K,T) */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * N-best (list) Viterbi (csrc/nbest.hip), 1 <= N <= 256, 1 <= K <= 16: the K most probable state
+ * paths of every sequence, in order, with their scores.  All arithmetic is fp32.
+ *   lo_t[j]   the log-emission: obs itself (HMM355_OBS_LOG) or the correctly rounded log(x + 1e-8)
+ *             (HMM355_OBS_PROB), the bits hmm355_viterbi_f32 uses
+ *   len       lengths[b] (clamped to [1, T] as read), or T with lengths == NULL
+ *   d_0[j][0] = init[j] + lo_0[j];  d_0[j][k] = -inf for k >= 1 (empty slots)
+ *   t >= 1:   the N*K candidates c(i, r) = fl(d_{t-1}[i][r] + log_P[i][j]) of state j are ordered by
+ *             value descending, ties by i ascending, then r ascending (all -inf candidates tie);
+ *             the k-th in that order gives d_t[j][k] = fl(c + lo_t[j]) and the back-pointer (i, r)
+ *   end:      the N*K values d_{len-1}[j][k] ordered the same way (value, then j, then k); the
+ *             first K are ranks 0 .. K-1, each path read back through the pointers
+ * fp32 addition is monotone, so scores[b, :] are exactly the K largest values over all N^len paths
+ * of the left-folded score fl(fl(s + log_P[z_{t-1}][z_t]) + lo_t[z_t]); the paths behind finite
+ * scores are pairwise distinct.  Rank 0 follows the rule of hmm355_viterbi_f32 (first index on
+ * ties, index 0 in a column without a finite candidate, first argmax at the last frame): its path
+ * and score are the states and final_score of hmm355_viterbi_f32 / hmm355_viterbi_ragged_f32.
+ *   paths   (B,K,T) int64;  scores (B,K) fp32, non-increasing in k
+ *   count   (B) int32 or NULL: the number of ranks with a score above -inf
+ * Rank 0 is always reported, even with score -inf.  Ranks k >= max(count, 1) do not exist (fewer
+ * than K paths with a score above -inf, or N^len < K): score -inf, states -1.  Frames
+ * t >= lengths[b] are never read (they may hold NaN) and get state -1.
+ * One workgroup per sequence runs exactly len steps, its final selection and the K backtraces:
+ * one launch, no waits between workgroups, no atomics; the same inputs give the same bits.
+ * workspace >= hmm355_viterbi_nbest_workspace_bytes: the back-pointers, (B,T,K,NP) uint16 with
+ * NP = N padded to 64/128/256, a pointer being 16 i + r.  That is B*T*K*NP*2 bytes: large, but
+ * linear in every size (B = 32, T = 2000, N = 256, K = 16: 500 MiB).
+ * Status, all before any launch: HMM355_E_ARG for a null pointer (lengths and count excepted),
+ * a bad obs_mode or B < 0; HMM355_E_STATES for N outside [1, 256] or K > 16; HMM355_E_SHAPE for
+ * T < 1, K < 1 or a size that overflows; HMM355_E_WORKSPACE for a short workspace; B == 0 is a
+ * no-op.  The size query returns 0 for a rejected shape.
+ * ------------------------------------------------------------------------------ */
+size_t hmm355_viterbi_nbest_workspace_bytes(int B, int T, int N, int K, int obs_mode);
+int hmm355_viterbi_nbest_f32(const float* obs, int obs_mode, const float* log_P, const float* init,
+                             const int* lengths /* (B) int32 device, or NULL */, int B, int T, int N, int K,
+                             int64_t* paths /* (B,K,T) */, float* scores /* (B,K) */, int* count /* (B) or NULL */,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Diagonal-covariance Gaussian-mixture emission scorer.  Replaces

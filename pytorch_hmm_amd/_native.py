@@ -76,6 +76,7 @@ EXPORTS = (
     "hmm355_viterbi_ragged_workspace_bytes", "hmm355_viterbi_ragged_f32", "hmm355_forward_backward_ragged_f32",
     "hmm355_ffbs_workspace_bytes", "hmm355_ffbs_f32",
     "hmm355_gmm_stats_workspace_bytes", "hmm355_gmm_stats_f32",
+    "hmm355_viterbi_nbest_workspace_bytes", "hmm355_viterbi_nbest_f32",
 )
 
 _lib = None
@@ -197,6 +198,10 @@ def lib():
     L.hmm355_gmm_stats_workspace_bytes.argtypes, L.hmm355_gmm_stats_workspace_bytes.restype = [I, I, I, I, I], S
     L.hmm355_gmm_stats_f32.argtypes = [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, S, P]
     L.hmm355_gmm_stats_f32.restype = I
+    L.hmm355_viterbi_nbest_workspace_bytes.argtypes = [I, I, I, I, I]
+    L.hmm355_viterbi_nbest_workspace_bytes.restype = S
+    L.hmm355_viterbi_nbest_f32.argtypes = [P, I, P, P, P, I, I, I, I, P, P, P, P, S, P]
+    L.hmm355_viterbi_nbest_f32.restype = I
     _lib = L
     return L
 

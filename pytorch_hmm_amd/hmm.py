@@ -140,6 +140,27 @@ class HMMPyTorch(HMM):
             return states.squeeze(0), delta.squeeze(0)
         return states, delta
 
+    def viterbi_nbest(self, observations: torch.Tensor, num_paths: int,
+                      lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Extension: the num_paths (at most 16) most probable state paths of every sequence, in
+        order, by list Viterbi (ops.viterbi_nbest, csrc/nbest.hip): (paths (B,K,T) int64, scores
+        (B,K)), (K,T) and (K) for 2-D input.  scores[b, k] is the fp32 log joint
+        log p0[z_0] + sum log P[z_{t-1}, z_t] + sum log(obs + 1e-8)[t, z_t] of path k, non-increasing
+        in k; rank 0 is viterbi_decode's path bit for bit.  A rank that does not exist (fewer than
+        num_paths paths with a score above -inf) has score -inf and states -1, as have the frames
+        past a sequence's length.  Takes no gradients (the inputs are detached).  For normalised
+        scores, log p(z | x), pass the paths to path_log_posterior."""
+        obs, squeeze = self._as_batch(observations)
+        B, T, K = obs.shape
+        assert K == self.K, f"Observation dim {K} must match model states {self.K}"
+        log_P, log_p0, _ = self._device_params(obs.device)
+        lens = ops.active_lengths(lengths, B, T, K)
+        paths, scores, _ = ops.viterbi_nbest(obs.detach(), log_P.detach(), log_p0.detach(), ops.OBS_PROB,
+                                             num_paths, lens)
+        if squeeze:
+            return paths.squeeze(0), scores.squeeze(0)
+        return paths, scores
+
     def _likelihood(self, observations, lengths, kind):
         """compute_likelihood ('ref') / log_likelihood ('exact'), taken at frame lengths[b] - 1."""
         obs, squeeze = self._as_batch(observations)

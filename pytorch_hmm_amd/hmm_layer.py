@@ -156,6 +156,16 @@ class HMMLayer(nn.Module):
             x = torch.sigmoid(x)
         return hmm.sample_posterior(x, num_samples, lengths, generator)
 
+    def nbest_alignment(self, x: torch.Tensor, num_paths: int, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The num_paths most probable alignments per sequence, in order (HMMPyTorch.viterbi_nbest),
+        on the emissions align() decodes: (paths (B,K,T) int64, scores (B,K)), (K,T) and (K) for 2-D
+        input.  Rank 0 is align()'s path; -1 in the frames past a sequence's length and in a rank
+        that does not exist.  No gradients."""
+        hmm = self._get_hmm()
+        if self.apply_sigmoid:
+            x = torch.sigmoid(x)
+        return hmm.viterbi_nbest(x, num_paths, lengths)
+
     def sample(self, seq_length: int, batch_size: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         return self._get_hmm().sample(seq_length, batch_size)
 
@@ -244,6 +254,14 @@ class GaussianHMMLayer(nn.Module):
 
     # -- Baum-Welch (em.py) ----------------------------------------------------------------
     _EM_UPDATES = ("transitions", "initial", "means", "variances")
+
+    def nbest_alignment(self, x: torch.Tensor, num_paths: int, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The num_paths most probable alignments per sequence under the Gaussian emissions
+        (HMMLayer.nbest_alignment on the observation probabilities): (paths (B,K,T) int64, scores
+        (B,K)).  No gradients."""
+        with torch.no_grad():
+            probs = self._observation_probs(x, lengths)
+        return self.hmm_layer.nbest_alignment(probs, num_paths, lengths)
 
     def _em_model(self):
         """(log_P, log_p0) of the E-step: log_softmax of the logits, or log of the fixed

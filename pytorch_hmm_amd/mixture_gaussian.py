@@ -269,6 +269,25 @@ class MixtureGaussianHMMLayer(nn.Module):
                                              generator=generator)
         return states
 
+    def nbest_alignment(self, x: torch.Tensor, num_paths: int, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The num_paths most probable alignments per sequence, in order (ops.viterbi_nbest with
+        OBS_LOG), under the model forward() decodes: the mixture emission log-probabilities, the log
+        transitions and the uniform initial vector -log S of its Viterbi.  (paths (B,K,T) int64,
+        scores (B,K)); rank 0 is forward()'s path and score; -1 in the frames past a sequence's
+        length and in a rank that does not exist.  No gradients."""
+        lens = ops.active_lengths(lengths, x.shape[0], x.shape[1], self.num_states)
+        if lens is not None:
+            valid = valid_frames(lens, x.shape[1], x.device)
+            x = torch.where(valid[..., None], x, torch.zeros_like(x))
+        with torch.no_grad():
+            log_T, log_w, init, _ = self._inference_tables(x.device)
+            if self.covariance_type != "full":
+                lp = ops.gmm_diag_logprob(x, self.means, self._component_log_vars(), log_w, 1)
+            else:
+                lp = self.get_observation_log_probs(x)
+            paths, scores, _ = ops.viterbi_nbest(lp, log_T, init, ops.OBS_LOG, num_paths, lens)
+        return paths, scores
+
     # -- Baum-Welch (em.py) ----------------------------------------------------------------
     _EM_UPDATES = ("transitions", "means", "variances", "weights")
 

@@ -45,6 +45,8 @@ lengths argument through `_lengths`.
       -> (gamma, grad_log_probs, grad_dur_lp)
   torch.ops.hmm355.ffbs(fwd, log_P, uniforms, lengths) -> states (B,K,T)     posterior path samples
   torch.ops.hmm355.gmm_stats(x, weight, means, log_vars, log_w, mix_lse, lengths) -> (occ, sx, sxx)
+  torch.ops.hmm355.viterbi_nbest(obs, log_P, init, obs_mode, num_paths, lengths)
+      -> (paths (B,K,T), scores (B,K), count (B))     the K best state paths, in order
 """
 import functools
 from typing import Optional, Tuple
@@ -428,6 +430,67 @@ def viterbi_ragged(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int,
 @viterbi_ragged.register_fake
 def _(obs, log_P, init, obs_mode, lengths):
     return _viterbi_outputs(obs.new_empty, *obs.shape)
+
+
+# ------------------------------------------------------------------- N-best Viterbi
+NBEST_MAX_PATHS = 16
+
+
+def _viterbi_nbest_outputs(mk, B, T, K):
+    """(paths, scores, count) of viterbi_nbest."""
+    return mk((B, K, T), dtype=_I64), mk((B, K), dtype=_F32), mk(B, dtype=_I32)
+
+
+def _viterbi_nbest_op():
+    """Registers hmm355::viterbi_nbest and its fake.  The op takes checked arguments (lengths: the
+    CPU tensor of ragged_lengths, or None); viterbi_nbest below is its caller."""
+    @torch.library.custom_op("hmm355::viterbi_nbest", mutates_args=())
+    def op(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int, num_paths: int,
+           lengths: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        nat.require_gpu(obs, log_P, init)
+        obs, log_P, init = _f32c(obs.detach()), _f32c(log_P.detach()), _f32c(init.detach())
+        B, T, N = obs.shape
+        dev = obs.device
+        paths, scores, count = outs = _viterbi_nbest_outputs(_on(dev), B, T, num_paths)
+        if B == 0:
+            return outs
+        lens = None if lengths is None else lengths.to(torch.int32).to(dev)
+        L = nat.lib()
+        _call(dev, L.hmm355_viterbi_nbest_f32, nat.ptr(obs), obs_mode, nat.ptr(log_P), nat.ptr(init), nat.ptr(lens),
+              B, T, N, num_paths, nat.ptr(paths), nat.ptr(scores), nat.ptr(count),
+              ws=L.hmm355_viterbi_nbest_workspace_bytes(B, T, N, num_paths, obs_mode))
+        return outs
+
+    @op.register_fake
+    def _(obs, log_P, init, obs_mode, num_paths, lengths=None):
+        return _viterbi_nbest_outputs(obs.new_empty, obs.shape[0], obs.shape[1], num_paths)
+
+
+_viterbi_nbest_op()
+
+
+def viterbi_nbest(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int, num_paths: int,
+                  lengths=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The num_paths = K most probable state paths of every sequence, in order (list Viterbi:
+    torch.ops.hmm355.viterbi_nbest over hmm355_viterbi_nbest_f32, csrc/nbest.hip; the recursion and
+    its tie order are spelled out in include/hmm355.h).  obs (B,T,N), log_P (N,N), init (N);
+    lengths: None or one length per sequence in any form ragged_lengths takes.  Returns
+    (paths (B,K,T) int64, scores (B,K) fp32 non-increasing in k, count (B) int32: the ranks with a
+    score above -inf).  Rank 0 is the path and final_score of viterbi / viterbi_ragged, bit for
+    bit; a rank k >= max(count, 1) does not exist and gets score -inf and states -1; frames
+    >= lengths[b] are never read and get state -1.  1 <= N <= 256, 1 <= K <= 16 (ValueError
+    beyond, raised here on the host).  No gradients: the inputs are detached."""
+    if obs.dim() != 3:
+        raise ValueError(f"obs must be (B, T, N); got {tuple(obs.shape)}")
+    B, T, N = obs.shape
+    K = int(num_paths)
+    if K < 1 or K > NBEST_MAX_PATHS:
+        raise ValueError(f"num_paths must lie in [1, {NBEST_MAX_PATHS}]; got {num_paths}")
+    if N > NARROW_MAX_STATES:
+        raise ValueError(f"N-best Viterbi supports at most {NARROW_MAX_STATES} states; got {N}")
+    host = None if lengths is None else ragged_lengths(lengths, B, T, N)
+    nat.require_gpu(obs, log_P, init)
+    return torch.ops.hmm355.viterbi_nbest(obs, log_P, init, obs_mode, K, host)
 
 
 # ------------------------------------------------------------------- GMM emission
