@@ -34,7 +34,7 @@ extern "C" {
 
 #define HMM355_OK 0
 #define HMM355_E_ARG (-1)       /* null pointer or negative size                      */
-#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]; emission statistics hmm355_gmm_stats_f32 C [1, 256], S*C <= 65536; N-best Viterbi hmm355_viterbi_nbest_f32 N [1, 256], K <= 16) */
+#define HMM355_E_STATES (-2)    /* N outside the entry point's range ([1, 256]; *_wide [1, 4096]; CTC Lmax [1, 2048]; DCHMM S [1, 256], group*S <= 4096; forced alignment Smax [1, 4096]; explicit-duration forced alignment Lmax [1, 1024], Dmax [1, 128], Lmax*Dmax <= 16384; posterior path sampling hmm355_ffbs_f32 [1, 256]; emission statistics hmm355_gmm_stats_f32 C [1, 256], S*C <= 65536; N-best Viterbi hmm355_viterbi_nbest_f32 N [1, 256], K <= 16; arc-list recursions hmm355_sparse_* N [1, HMM355_SPARSE_MAX_STATES = 8192], with E outside [1, HMM355_SPARSE_MAX_ARCS = 2^20] an HMM355_E_SHAPE) */
 #define HMM355_E_SHAPE (-3)     /* T < 1 (DTW: N < 1 or M < 1), or a size product overflows */
 #define HMM355_E_WORKSPACE (-4) /* workspace smaller than *_workspace_bytes() reports   */
 #define HMM355_E_DURATION (-5)  /* HSMM max_duration outside [1, 1024] (hmm355_hsmm_fb_f32: [1, 128], S * Dmax <= 16384) */
@@ -370,6 +370,83 @@ int hmm355_viterbi_nbest_f32(const float* obs, int obs_mode, const float* log_P,
                              const int* lengths /* (B) int32 device, or NULL */, int B, int T, int N, int K,
                              int64_t* paths /* (B,K,T) */, float* scores /* (B,K) */, int* count /* (B) or NULL */,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * HMM recursions over an arc list: a sparse transition matrix (csrc/sparse.hip).
+ * 1 <= N <= HMM355_SPARSE_MAX_STATES states, 1 <= E <= HMM355_SPARSE_MAX_ARCS arcs
+ * (src[e], dst[e], log_w[e]) shared by the batch; self-loops and log_w = -inf are allowed, a
+ * (src, dst) pair appears at most once (the caller's duty).  The model is exactly the dense one
+ * whose log_P is -inf off the arcs.  log_obs (B,T,N) holds log-emissions (HMM355_OBS_LOG only);
+ * lengths is (B) int32 on the device or NULL (= T everywhere), clamped to [1, T] as read; frames
+ * t >= lengths[b] are never read (they may hold NaN).  The cost of a step is proportional to E.
+ *
+ * The arcs come sorted, grouped by an owner state, as a row-pointer array and two arc arrays:
+ *   in_*   by destination, source ascending within a destination: state j owns the arcs
+ *          in_ptr[j] .. in_ptr[j+1]-1, in_src[k] is the arc's source, in_log_w[k] its weight
+ *   out_*  by source: state i owns out_ptr[i] .. out_ptr[i+1]-1, out_dst[k], out_log_w[k]
+ * A row-pointer array is passed twice with the same N+1 values: *_ptr_host in host memory, checked
+ * before any launch (non-decreasing from 0 to E, else HMM355_E_ARG; its largest difference selects
+ * the kernel: up to 4 arcs per state, 3 above 4096 states, stay in registers for the whole
+ * sequence, more are read through L2 every step, and a state with more than 64 is taken by a
+ * whole wave), and *_ptr in
+ * device memory, read by the kernels.  As read on the device a row pointer is clamped into [0, E]
+ * and a state id into [0, N), so a wrong device array cannot index out of bounds.
+ *
+ * One workgroup per (sequence, job) -- the Viterbi chain with its backtrace, the alpha chain, the
+ * beta chain -- running exactly lengths[b] steps with the state rows in LDS; one launch for the
+ * chains, no waits between workgroups, no atomics: the same inputs give the same bits.
+ *
+ * hmm355_sparse_viterbi_f32: all fp32,
+ *   delta_0 = init + e_0;  delta_t[j] = fl(max over in-arcs of fl(delta_{t-1}[src] + log_w) + e_t[j])
+ * candidates in ascending source with strict >; a destination whose maximum is -inf (no in-arcs,
+ * or every candidate -inf) gets delta = -inf and back-pointer 0; the final state is the first
+ * argmax of delta_{len-1}.  states (B,T) int64, log_delta (B,T,N), final_score (B) or NULL are
+ * bit-identical to hmm355_viterbi_f32 / _ragged_f32 / _wide_f32 on the densified matrix.  Padded
+ * frames: state -1, log_delta -inf.  workspace: the back-pointers, (B,T,N rounded up to 8) uint16.
+ *
+ * hmm355_sparse_forward_backward_f32: the scaled probability-domain recursion with a deferred
+ * normaliser (as hmm355_forward_backward_ragged_f32), e_t = exp(log_obs_t - max_j log_obs_t), the
+ * log-scales summed in fp64 after the chains.  loglik (B); posterior (B,T,N) or NULL: gamma, 0 in
+ * padded frames.  A sequence with no path of positive probability gets loglik -inf and exact
+ * zeros in posterior.  The workspace keeps the scaled rows U, V (B,T,N fp32 each), the step
+ * normalisers and two per-frame factors for hmm355_sparse_arc_counts_f32.
+ *
+ * hmm355_sparse_arc_counts_f32, after a forward-backward call with the same log_obs, lengths and
+ * sizes, whose workspace is fb_workspace:
+ *   xi[e] = sum_b weight[b] sum_{1 <= t < lengths[b]} P(z_{t-1} = src[e], z_t = dst[e] | x_b)
+ * (weight (B) fp32 or NULL = 1), in the order of the src / dst / log_w arrays given (any order).
+ * xi is (E) fp64: a thread per arc, per-tile partial sums in fp64 added in tile order, no atomics.
+ * An arc with log_w = -inf and every arc of a sequence with no path count exactly 0.
+ *
+ * Status, every check before any launch: HMM355_E_ARG for B < 0, a null pointer (lengths,
+ * final_score, posterior and weight excepted) or a bad row-pointer array; HMM355_E_STATES for N
+ * outside [1, 8192]; HMM355_E_SHAPE for E outside [1, 2^20], T < 1 or a size that overflows;
+ * HMM355_E_WORKSPACE for a short workspace; B == 0 is a no-op.  The size queries return 0 for a
+ * rejected shape.
+ * ------------------------------------------------------------------------------ */
+#define HMM355_SPARSE_MAX_STATES 8192
+#define HMM355_SPARSE_MAX_ARCS 1048576 /* 2^20 */
+size_t hmm355_sparse_viterbi_workspace_bytes(int B, int T, int N, int E);
+int hmm355_sparse_viterbi_f32(const float* log_obs, const int* in_ptr_host /* (N+1) host */,
+                              const int* in_ptr /* (N+1) device */, const int* in_src /* (E) */,
+                              const float* in_log_w /* (E) */, const float* init /* (N) */,
+                              const int* lengths /* (B) int32 device, or NULL */, int B, int T, int N, int E,
+                              int64_t* states /* (B,T) */, float* log_delta /* (B,T,N) */,
+                              float* final_score /* (B) or NULL */, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t hmm355_sparse_forward_backward_workspace_bytes(int B, int T, int N, int E);
+int hmm355_sparse_forward_backward_f32(const float* log_obs, const int* in_ptr_host, const int* in_ptr,
+                                       const int* in_src, const float* in_log_w, const int* out_ptr_host,
+                                       const int* out_ptr, const int* out_dst, const float* out_log_w,
+                                       const float* log_p0 /* (N) */, const int* lengths, int B, int T, int N, int E,
+                                       float* loglik /* (B) */, float* posterior /* (B,T,N) or NULL */,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+size_t hmm355_sparse_arc_counts_workspace_bytes(int B, int T, int N, int E);
+int hmm355_sparse_arc_counts_f32(const float* log_obs, const int* src /* (E) device */, const int* dst /* (E) */,
+                                 const float* log_w /* (E) */, const float* weight /* (B) or NULL */,
+                                 const int* lengths, int B, int T, int N, int E, const void* fb_workspace,
+                                 size_t fb_workspace_bytes, double* xi /* (E) */, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Diagonal-covariance Gaussian-mixture emission scorer.  Replaces

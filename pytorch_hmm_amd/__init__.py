@@ -49,3 +49,8 @@ from . import em
 from .em import EStats, e_step, gaussian_m_step, transition_m_step
 
 __all__ += ["em", "EStats", "e_step", "transition_m_step", "gaussian_m_step"]
+
+from . import sparse
+from .sparse import SparseHMM, SparseTransitions, sparse_transition_m_step
+
+__all__ += ["sparse", "SparseHMM", "SparseTransitions", "sparse_transition_m_step"]

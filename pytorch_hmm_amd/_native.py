@@ -47,6 +47,8 @@ DURFORCED_MAX_POSITIONS = 1024  # HMM355_DURFORCED_MAX_POSITIONS
 DURFORCED_MAX_DURATION = 128  # HMM355_DURFORCED_MAX_DURATION
 DURFORCED_MAX_CELLS = 16384  # HMM355_DURFORCED_MAX_CELLS: positions times max_duration
 GMM_STATS_MAX_DIM = 1024  # HMM355_GMM_STATS_MAX_DIM
+SPARSE_MAX_STATES = 8192  # HMM355_SPARSE_MAX_STATES
+SPARSE_MAX_ARCS = 1 << 20  # HMM355_SPARSE_MAX_ARCS
 
 # every symbol include/hmm355.h declares (checked by tests/test_native_abi.py)
 EXPORTS = (
@@ -77,6 +79,9 @@ EXPORTS = (
     "hmm355_ffbs_workspace_bytes", "hmm355_ffbs_f32",
     "hmm355_gmm_stats_workspace_bytes", "hmm355_gmm_stats_f32",
     "hmm355_viterbi_nbest_workspace_bytes", "hmm355_viterbi_nbest_f32",
+    "hmm355_sparse_viterbi_workspace_bytes", "hmm355_sparse_viterbi_f32",
+    "hmm355_sparse_forward_backward_workspace_bytes", "hmm355_sparse_forward_backward_f32",
+    "hmm355_sparse_arc_counts_workspace_bytes", "hmm355_sparse_arc_counts_f32",
 )
 
 _lib = None
@@ -202,6 +207,15 @@ def lib():
     L.hmm355_viterbi_nbest_workspace_bytes.restype = S
     L.hmm355_viterbi_nbest_f32.argtypes = [P, I, P, P, P, I, I, I, I, P, P, P, P, S, P]
     L.hmm355_viterbi_nbest_f32.restype = I
+    for name in ("viterbi", "forward_backward", "arc_counts"):
+        q = getattr(L, f"hmm355_sparse_{name}_workspace_bytes")
+        q.argtypes, q.restype = [I, I, I, I], S
+    L.hmm355_sparse_viterbi_f32.argtypes = [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, S, P]
+    L.hmm355_sparse_viterbi_f32.restype = I
+    L.hmm355_sparse_forward_backward_f32.argtypes = [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, S, P]
+    L.hmm355_sparse_forward_backward_f32.restype = I
+    L.hmm355_sparse_arc_counts_f32.argtypes = [P, P, P, P, P, P, I, I, I, I, P, S, P, P, S, P]
+    L.hmm355_sparse_arc_counts_f32.restype = I
     _lib = L
     return L
 

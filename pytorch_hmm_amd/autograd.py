@@ -825,3 +825,53 @@ class HsmmLogLik(torch.autograd.Function):
                  torch.einsum("b,bij->ij", g, trans_c) if need[2] else None,
                  torch.einsum("b,bs->s", g, init_p) if need[3] else None]
         return tuple(None if x is None else x.to(dt) for x, dt in zip(grads, ctx.dtypes))
+
+
+class SparseLogLik(torch.autograd.Function):
+    """loglik (B) of a padded batch under an HMM whose transitions are an arc list
+    (sparse.SparseTransitions; ops.sparse_forward_backward, csrc/sparse.hip), differentiable in
+
+        log_obs (B,T,N)   d loglik[b] / d log_obs[b,t,j] = gamma[b,t,j]
+        log_w   (E)       d sum_b g_b loglik[b] / d log_w[e] = xi[e], the expected number of times
+                          arc e is taken, in the caller's arc order (ops.sparse_arc_counts with g)
+        log_p0  (N)       d loglik[b] / d log_p0[j] = gamma[b,0,j]
+
+    The forward asks for the posterior only when log_obs or log_p0 needs a gradient and keeps the
+    workspace only when log_w does; the backward forms xi in one call with the incoming gradient as
+    the per-sequence weight.  A sequence with no path (loglik = -inf) and padded frames contribute
+    exact zeros.  This is the gradient of more than 256 states that SequenceLogLik refuses.
+
+        loglik = SparseLogLik.apply(log_obs, log_w, log_p0, transitions, lengths)
+
+    lengths: host int64 (B) from ops.ragged_lengths, or None."""
+
+    @staticmethod
+    def forward(ctx, log_obs, log_w, log_p0, transitions, lengths=None):
+        tr = transitions
+        nat.require_gpu(log_obs, log_w, log_p0)
+        obs = log_obs.detach().to(torch.float32).contiguous()
+        w = log_w.detach().to(torch.float32)
+        need = ctx.needs_input_grad
+        want_post = bool(need[0] or need[2])
+        loglik, post, ws = ops.sparse_forward_backward(
+            obs, tr.in_ptr_host, tr.in_ptr, tr.in_src, w[tr.perm_in].contiguous(), tr.out_ptr_host, tr.out_ptr,
+            tr.out_dst, w[tr.perm_out].contiguous(), log_p0.detach(), want_post, lengths)
+        ctx.transitions, ctx.lengths = tr, lengths
+        ctx.dtypes = (log_obs.dtype, log_w.dtype, log_p0.dtype)
+        ctx.save_for_backward(post if want_post else None, *((obs, w, ws) if need[1] else (None, None, None)))
+        return loglik
+
+    @staticmethod
+    def backward(ctx, grad_loglik):
+        post, obs, w, ws = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        tr = ctx.transitions
+        g = grad_loglik.to(torch.float32).contiguous()
+        g_obs = g_w = g_p0 = None
+        if need[0]:
+            g_obs = (post * g[:, None, None]).to(ctx.dtypes[0])
+        if need[2]:
+            g_p0 = (post[:, 0] * g[:, None]).sum(0).to(ctx.dtypes[2])
+        if need[1]:
+            g_w = ops.sparse_arc_counts(obs, tr.src, tr.dst, w.contiguous(), ws, g, ctx.lengths).to(ctx.dtypes[1])
+        return g_obs, g_w, g_p0, None, None

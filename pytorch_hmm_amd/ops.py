@@ -47,6 +47,12 @@ lengths argument through `_lengths`.
   torch.ops.hmm355.gmm_stats(x, weight, means, log_vars, log_w, mix_lse, lengths) -> (occ, sx, sxx)
   torch.ops.hmm355.viterbi_nbest(obs, log_P, init, obs_mode, num_paths, lengths)
       -> (paths (B,K,T), scores (B,K), count (B))     the K best state paths, in order
+  torch.ops.hmm355.sparse_viterbi(obs, in_ptr_host, in_ptr, in_src, in_log_w, init, lengths)
+      -> (states, log_delta, final_score)             Viterbi over an arc list, N <= 8192
+  torch.ops.hmm355.sparse_forward_backward(obs, in_ptr_host, in_ptr, in_src, in_log_w, out_ptr_host, out_ptr,
+                                           out_dst, out_log_w, log_p0, want_posterior, lengths)
+      -> (loglik (B), posterior (B,T,N), workspace)   the sums over an arc list
+  torch.ops.hmm355.sparse_arc_counts(obs, src, dst, log_w, workspace, weight, lengths) -> xi (E) fp64
 """
 import functools
 from typing import Optional, Tuple
@@ -491,6 +497,163 @@ def viterbi_nbest(obs: Tensor, log_P: Tensor, init: Tensor, obs_mode: int, num_p
     host = None if lengths is None else ragged_lengths(lengths, B, T, N)
     nat.require_gpu(obs, log_P, init)
     return torch.ops.hmm355.viterbi_nbest(obs, log_P, init, obs_mode, K, host)
+
+
+# ------------------------------------------------------------- sparse transitions (arc list)
+SPARSE_MAX_STATES = nat.SPARSE_MAX_STATES
+SPARSE_MAX_ARCS = nat.SPARSE_MAX_ARCS
+
+
+def _sparse_viterbi_outputs(mk, B, T, N):
+    """(states, log_delta, final_score) of sparse_viterbi."""
+    return mk((B, T), dtype=_I64), mk((B, T, N), dtype=_F32), mk(B, dtype=_F32)
+
+
+def _sparse_fb_outputs(mk, B, T, N, E, want_posterior):
+    """(loglik, posterior, workspace) of sparse_forward_backward; the workspace's size is the
+    library's answer (a host function), so the fake gives the same shape."""
+    nbytes = nat.lib().hmm355_sparse_forward_backward_workspace_bytes(B, T, N, E) if B else 0
+    return (mk(B, dtype=_F32), mk((B, T, N) if want_posterior else _EMPTY, dtype=_F32),
+            mk(max(int(nbytes), 1), dtype=torch.uint8))
+
+
+def _sparse_counts_outputs(mk, E):
+    """xi of sparse_arc_counts."""
+    return mk(E, dtype=torch.float64)
+
+
+def _dev_lengths(lengths, dev):
+    return None if lengths is None else lengths.to(torch.int32).to(dev)
+
+
+def _sparse_ops():
+    """Registers hmm355::sparse_viterbi, ::sparse_forward_backward and ::sparse_arc_counts with their
+    fakes.  The ops take checked arguments: the sorted arc arrays of sparse.SparseTransitions (a
+    row-pointer array twice, as a CPU int32 tensor and on the device) and lengths as the CPU tensor
+    of ragged_lengths, or None; the functions below are their callers."""
+    @torch.library.custom_op("hmm355::sparse_viterbi", mutates_args=())
+    def vit(obs: Tensor, in_ptr_host: Tensor, in_ptr: Tensor, in_src: Tensor, in_log_w: Tensor, init: Tensor,
+            lengths: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        nat.require_gpu(obs, in_ptr, in_src, in_log_w, init)
+        obs, w, init = _f32c(obs.detach()), _f32c(in_log_w.detach()), _f32c(init.detach())
+        B, T, N = obs.shape
+        E = w.numel()
+        dev = obs.device
+        states, delta, final = outs = _sparse_viterbi_outputs(_on(dev), B, T, N)
+        if B == 0:
+            return outs
+        lens = _dev_lengths(lengths, dev)
+        L = nat.lib()
+        _call(dev, L.hmm355_sparse_viterbi_f32, nat.ptr(obs), nat.ptr(in_ptr_host), nat.ptr(in_ptr), nat.ptr(in_src),
+              nat.ptr(w), nat.ptr(init), nat.ptr(lens), B, T, N, E, nat.ptr(states), nat.ptr(delta), nat.ptr(final),
+              ws=L.hmm355_sparse_viterbi_workspace_bytes(B, T, N, E))
+        return outs
+
+    @vit.register_fake
+    def _(obs, in_ptr_host, in_ptr, in_src, in_log_w, init, lengths=None):
+        return _sparse_viterbi_outputs(obs.new_empty, *obs.shape)
+
+    @torch.library.custom_op("hmm355::sparse_forward_backward", mutates_args=())
+    def fb(obs: Tensor, in_ptr_host: Tensor, in_ptr: Tensor, in_src: Tensor, in_log_w: Tensor,
+           out_ptr_host: Tensor, out_ptr: Tensor, out_dst: Tensor, out_log_w: Tensor, log_p0: Tensor,
+           want_posterior: bool, lengths: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        nat.require_gpu(obs, in_ptr, in_src, in_log_w, out_ptr, out_dst, out_log_w, log_p0)
+        obs, wi, wo, p0 = (_f32c(t.detach()) for t in (obs, in_log_w, out_log_w, log_p0))
+        B, T, N = obs.shape
+        E = wi.numel()
+        dev = obs.device
+        loglik, post, ws = outs = _sparse_fb_outputs(_on(dev), B, T, N, E, want_posterior)
+        if B == 0:
+            return outs
+        lens = _dev_lengths(lengths, dev)
+        L = nat.lib()
+        _call(dev, L.hmm355_sparse_forward_backward_f32, nat.ptr(obs), nat.ptr(in_ptr_host), nat.ptr(in_ptr),
+              nat.ptr(in_src), nat.ptr(wi), nat.ptr(out_ptr_host), nat.ptr(out_ptr), nat.ptr(out_dst), nat.ptr(wo),
+              nat.ptr(p0), nat.ptr(lens), B, T, N, E, nat.ptr(loglik), _opt(post, want_posterior), ws=ws)
+        return outs
+
+    @fb.register_fake
+    def _(obs, in_ptr_host, in_ptr, in_src, in_log_w, out_ptr_host, out_ptr, out_dst, out_log_w, log_p0,
+          want_posterior, lengths=None):
+        return _sparse_fb_outputs(obs.new_empty, *obs.shape, in_log_w.numel(), want_posterior)
+
+    @torch.library.custom_op("hmm355::sparse_arc_counts", mutates_args=())
+    def counts(obs: Tensor, src: Tensor, dst: Tensor, log_w: Tensor, workspace: Tensor,
+               weight: Optional[Tensor] = None, lengths: Optional[Tensor] = None) -> Tensor:
+        nat.require_gpu(obs, src, dst, log_w, workspace, weight)
+        obs, w = _f32c(obs.detach()), _f32c(log_w.detach())
+        g = None if weight is None else _f32c(weight.detach())
+        B, T, N = obs.shape
+        E = w.numel()
+        dev = obs.device
+        if B == 0:
+            return torch.zeros(E, dtype=torch.float64, device=dev)
+        xi = _sparse_counts_outputs(_on(dev), E)
+        lens = _dev_lengths(lengths, dev)
+        L = nat.lib()
+        _call(dev, L.hmm355_sparse_arc_counts_f32, nat.ptr(obs), nat.ptr(src), nat.ptr(dst), nat.ptr(w), nat.ptr(g),
+              nat.ptr(lens), B, T, N, E, nat.ptr(workspace), workspace.numel(), nat.ptr(xi),
+              ws=L.hmm355_sparse_arc_counts_workspace_bytes(B, T, N, E))
+        return xi
+
+    @counts.register_fake
+    def _(obs, src, dst, log_w, workspace, weight=None, lengths=None):
+        return _sparse_counts_outputs(obs.new_empty, log_w.numel())
+
+
+_sparse_ops()
+
+
+def _sparse_check(obs, ptr_host, N_of, what):
+    if obs.dim() != 3:
+        raise ValueError(f"log_obs must be (B, T, N); got {tuple(obs.shape)}")
+    N = obs.shape[2]
+    if N < 1 or N > SPARSE_MAX_STATES:
+        raise ValueError(f"{what} supports 1 to {SPARSE_MAX_STATES} states; got {N}")
+    if ptr_host.numel() != N + 1 or N_of.numel() != N:
+        raise ValueError(f"the transitions have {ptr_host.numel() - 1} states and the initial scores {N_of.numel()}; "
+                         f"log_obs has {N}")
+
+
+def sparse_viterbi(obs: Tensor, in_ptr_host: Tensor, in_ptr: Tensor, in_src: Tensor, in_log_w: Tensor,
+                   init: Tensor, lengths=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Viterbi over an arc list (torch.ops.hmm355.sparse_viterbi over hmm355_sparse_viterbi_f32,
+    csrc/sparse.hip): obs (B,T,N) log-emissions, the arcs sorted by destination as
+    sparse.SparseTransitions keeps them (in_ptr_host: CPU int32 (N+1); in_ptr, in_src, in_log_w on
+    the device), init (N).  lengths: None or one length per sequence in any form ragged_lengths
+    takes (no 256-state limit here).  Returns (states (B,T) int64, log_delta (B,T,N), final_score
+    (B)), bit-identical to viterbi / viterbi_ragged on the dense matrix that is -inf off the arcs;
+    padded frames get state -1 and log_delta -inf.  1 <= N <= 8192.  No gradients."""
+    _sparse_check(obs, in_ptr_host, init, "sparse Viterbi")
+    host = None if lengths is None else ragged_lengths(lengths, obs.shape[0], obs.shape[1])
+    nat.require_gpu(obs, in_ptr, in_src, in_log_w, init)
+    return torch.ops.hmm355.sparse_viterbi(obs, in_ptr_host, in_ptr, in_src, in_log_w, init, host)
+
+
+def sparse_forward_backward(obs: Tensor, in_ptr_host: Tensor, in_ptr: Tensor, in_src: Tensor, in_log_w: Tensor,
+                            out_ptr_host: Tensor, out_ptr: Tensor, out_dst: Tensor, out_log_w: Tensor,
+                            log_p0: Tensor, want_posterior: bool = True,
+                            lengths=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The sums over an arc list (hmm355_sparse_forward_backward_f32): (loglik (B), posterior
+    (B,T,N) or an empty tensor, workspace).  The workspace (a device byte tensor holding the scaled
+    rows) is what sparse_arc_counts reads.  Padded frames have posterior 0; a sequence with no
+    path gets loglik -inf and zeros.  Arguments as sparse_viterbi, with the arcs in both orders."""
+    _sparse_check(obs, in_ptr_host, log_p0, "sparse forward-backward")
+    host = None if lengths is None else ragged_lengths(lengths, obs.shape[0], obs.shape[1])
+    nat.require_gpu(obs, in_ptr, in_src, in_log_w, out_ptr, out_dst, out_log_w, log_p0)
+    return torch.ops.hmm355.sparse_forward_backward(obs, in_ptr_host, in_ptr, in_src, in_log_w, out_ptr_host,
+                                                    out_ptr, out_dst, out_log_w, log_p0, bool(want_posterior), host)
+
+
+def sparse_arc_counts(obs: Tensor, src: Tensor, dst: Tensor, log_w: Tensor, workspace: Tensor, weight=None,
+                      lengths=None) -> Tensor:
+    """xi (E) fp64, in the order of src / dst / log_w (int32, int32, fp32 on the device): the
+    expected number of times each arc is taken, summed over the batch with the per-sequence
+    `weight` (B) or 1 (hmm355_sparse_arc_counts_f32).  workspace: sparse_forward_backward's, from
+    the same obs and lengths.  Two calls give the same bits."""
+    host = None if lengths is None else ragged_lengths(lengths, obs.shape[0], obs.shape[1])
+    nat.require_gpu(obs, src, dst, log_w, workspace)
+    return torch.ops.hmm355.sparse_arc_counts(obs, src, dst, log_w, workspace, weight, host)
 
 
 # ------------------------------------------------------------------- GMM emission
