@@ -87,6 +87,25 @@ int hmm355_version(void);
  *   lik_ref    (B) or NULL: the reference's compute_likelihood value
  *              logsumexp_j(log(exp(log alpha_{T-1}[j]) + 1e-8))  (hmm.py:206)
  *   workspace  >= hmm355_fb_workspace_bytes(B,T,N) bytes of device memory
+ *
+ * Range contract of every sum-product entry point of this library (forward-backward: plan, ex,
+ * ragged, wide, tv; the sparse sums and arc counts).  State probabilities are fp32, rescaled once
+ * per step by one factor for the whole row, and with HMM355_OBS_LOG a frame's emissions are
+ * e_t = exp(obs_t - M_t) with M_t the maximum over ALL states: a state more than about 87 nats
+ * behind its row's leader is exactly 0.  The results are those of the exact sums (to fp32
+ * rounding) whenever the leader can pass its mass on -- always with a floored table
+ * (log(P + 1e-8): the leader refills every state at -18.4 nats per step).  With exact zeros
+ * (-inf) in log_P or log_p0 the leader may be a state that no path reaches or that leads
+ * nowhere; the states that carry the sequence's probability are then flushed and a feasible
+ * sequence comes back with loglik -inf and a zero posterior, or with a finite but wrong loglik.
+ * Such a call still fails cleanly: no NaN in loglik, posterior, forward or backward (nor in the
+ * sparse arc counts), loglik finite or -inf, every posterior row a distribution or all zero
+ * (csrc/common.h rcp_normal / row_value / clean_loglik), other sequences of the batch
+ * untouched.  These entry points do not detect the condition.  The rows they leave (U, V, CA
+ * below; the sparse workspace) are enough to: pytorch_hmm_amd/range_guard.py flags the affected
+ * sequences from them and recomputes those in float64 log space, and the package's E-step and
+ * likelihood entry points do so by default.  The batch-tiled form (wide, N > 256)
+ * leaves no such rows to the package: it stays unguarded.
  * ------------------------------------------------------------------------------ */
 size_t hmm355_fb_workspace_bytes(int B, int T, int N);
 /* Same as hmm355_forward_backward_f32 with a custom terminal backward vector:

@@ -54,3 +54,7 @@ from . import sparse
 from .sparse import SparseHMM, SparseTransitions, sparse_transition_m_step
 
 __all__ += ["sparse", "SparseHMM", "SparseTransitions", "sparse_transition_m_step"]
+
+from . import range_guard
+
+__all__ += ["range_guard"]

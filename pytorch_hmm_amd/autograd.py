@@ -31,6 +31,7 @@ import torch
 
 from . import _native as nat
 from . import ops
+from . import range_guard as rg
 
 
 def needs_grad(*tensors) -> bool:
@@ -145,21 +146,51 @@ def _terminal_adjoint(a_last, kind):
     return g, log_mu
 
 
+def _guard_replace(grads, bad, gout, obs, lP, l0, lengths):
+    """(grad_obs, grad_lP, grad_l0) with the flagged sequences' share -- which the callers zeroed
+    -- taken from the log-space loop: d loglik_b / d log_obs = gamma_b, d / d log_P = xi_b,
+    d / d log_p0 = gamma_b[0], times the incoming gradient."""
+    grad_obs, grad_lP, grad_l0 = grads
+    g = gout[bad].to(torch.float64)
+    lens = None if lengths is None else lengths.to(obs.device)[bad]
+    _, gam, xi = rg.logspace_forward_backward(obs[bad], l0, lP, lengths=lens, weight=g, want_xi=grad_lP is not None)
+    gam = gam * g[:, None, None]
+    grad_obs = grad_obs.index_copy(0, bad, gam.to(grad_obs.dtype))
+    grad_l0 = grad_l0 + gam[:, 0].sum(0).to(grad_l0.dtype)
+    if grad_lP is not None:
+        grad_lP = grad_lP + xi.to(grad_lP.dtype)
+    return grad_obs, grad_lP, grad_l0
+
+
 class SequenceLogLik(torch.autograd.Function):
     """(B,) log-likelihood of each sequence ('ref' or 'exact'), differentiable in obs,
-    log_P and log_p0."""
+    log_P and log_p0.
+
+    range_guard (default on; 'exact' with OBS_LOG only): a sequence that left the kernels' fp32
+    range (range_guard.out_of_range; possible only with exact zeros in log_P) takes its value and,
+    in the backward, its gradients from the float64 log-space loop
+    (range_guard.logspace_forward_backward), the others keep the kernels' bits.  One host read of a
+    flag per forward; skipped while a CUDA graph is being captured."""
 
     @staticmethod
-    def forward(ctx, obs, log_P, log_p0, obs_mode, kind, plan=None, lengths=None):
+    def forward(ctx, obs, log_P, log_p0, obs_mode, kind, plan=None, lengths=None, range_guard=True):
         """lengths: host int64 (B) from ops.ragged_lengths, or None.  With it sequence b is
         obs[b, :lengths[b]] (the ragged entry point); the gradients are those of the per-sequence
         computations, grad_obs exactly 0 in the padded frames."""
         _require_narrow(obs.shape[-1], "the gradient of the sequence log-likelihood")
         nat.require_gpu(obs, log_P, log_p0)
         obs_c, lP, l0 = (t.detach().to(torch.float32).contiguous() for t in (obs, log_P, log_p0))
-        _, loglik, lik_ref, *_ = _run_fb(obs_c, lP, l0, obs_mode, plan=plan, lengths=lengths)
+        _, loglik, lik_ref, U, V, _, _, CA, CB = _run_fb(obs_c, lP, l0, obs_mode, plan=plan, lengths=lengths)
+        bad = None
+        if range_guard and kind == "exact" and obs_mode == nat.OBS_LOG:
+            valid = valid_frames(lengths, obs_c.shape[1], obs_c.device)
+            bad = rg.flagged(U, V, CA, lengths, E=_staged_emissions(obs_c, obs_mode, valid), CB=CB)
+            if bad is not None:
+                lens = None if lengths is None else lengths.to(obs_c.device)[bad]
+                ll, _, _ = rg.logspace_forward_backward(obs_c[bad], l0, lP, lengths=lens, want_xi=False)
+                loglik = loglik.index_copy(0, bad, ll.to(loglik.dtype))
         ctx.save_for_backward(obs_c, lP, l0)
-        ctx.obs_mode, ctx.kind, ctx.plan, ctx.lengths = obs_mode, kind, plan, lengths
+        ctx.obs_mode, ctx.kind, ctx.plan, ctx.lengths, ctx.bad = obs_mode, kind, plan, lengths, bad
         return lik_ref if kind == "ref" else loglik
 
     @staticmethod
@@ -174,6 +205,11 @@ class SequenceLogLik(torch.autograd.Function):
         G = g.sum(-1) * gout                                      # (B,)
         post, _, _, U, V, _, _, CA, _ = _run_fb(obs, lP, l0, ctx.obs_mode, log_beta_T=log_mu.contiguous(),
                                                 posterior=True, plan=ctx.plan)
+        bad = ctx.bad
+        if bad is not None:
+            # the flagged sequences' rows may hold anything (NaN included): out of every factor
+            G, post, U, V = (x.index_fill(0, bad, 0.0) for x in (G, post, U, V))
+            CA = CA.index_fill(0, bad, 1.0)
         grad_lo = G[:, None, None] * post
         if ctx.obs_mode == nat.OBS_PROB:
             grad_obs = grad_lo / (obs + 1e-8)
@@ -191,10 +227,14 @@ class SequenceLogLik(torch.autograd.Function):
             c = CA                                                # U_{t+1} = A^T U_t e_{t+1} / c_t
             S = (U * V).sum(-1)                                   # (B,T)
             X = U[:, :-1] / (c[:, :-1] * S[:, 1:]).unsqueeze(-1) * G[:, None, None]
+            if bad is not None:
+                X = X.index_fill(0, bad, 0.0)                     # 0 / (1 * 0) above
             Y = e[:, 1:] * V[:, 1:]
             M = torch.einsum("bti,btj->ij", X, Y)
             grad_lP = torch.exp(lP) * M
-        return grad_obs, grad_lP, grad_l0, None, None, None, None
+        if bad is not None:
+            grad_obs, grad_lP, grad_l0 = _guard_replace((grad_obs, grad_lP, grad_l0), bad, gout, obs, lP, l0, None)
+        return grad_obs, grad_lP, grad_l0, None, None, None, None, None
 
     @staticmethod
     def _backward_ragged(ctx, gout):
@@ -214,6 +254,10 @@ class SequenceLogLik(torch.autograd.Function):
         G = g.sum(-1) * gout
         post, _, _, U, V, _, _, CA, _ = _run_fb(obs, lP, l0, ctx.obs_mode, log_beta_T=log_mu.contiguous(),
                                                 posterior=True, lengths=lengths)
+        bad = ctx.bad
+        if bad is not None:
+            G, post, U, V = (x.index_fill(0, bad, 0.0) for x in (G, post, U, V))
+            CA = CA.index_fill(0, bad, 1.0)
         grad_lo = G[:, None, None] * post                         # post is 0 in the padded frames
         e = _staged_emissions(obs, ctx.obs_mode, valid)
         if ctx.obs_mode == nat.OBS_PROB:
@@ -228,9 +272,13 @@ class SequenceLogLik(torch.autograd.Function):
             den = (CA[:, :-1] * S[:, 1:]).unsqueeze(-1)
             X = torch.where(pair, U[:, :-1] / torch.where(pair, den, torch.ones_like(den)), torch.zeros_like(U[:, :-1]))
             X = X * G[:, None, None]
+            if bad is not None:
+                X = X.index_fill(0, bad, 0.0)
             Y = e[:, 1:] * V[:, 1:]
             grad_lP = torch.exp(lP) * torch.einsum("bti,btj->ij", X, Y)
-        return grad_obs, grad_lP, grad_l0, None, None, None, None
+        if bad is not None:
+            grad_obs, grad_lP, grad_l0 = _guard_replace((grad_obs, grad_lP, grad_l0), bad, gout, obs, lP, l0, lengths)
+        return grad_obs, grad_lP, grad_l0, None, None, None, None, None
 
 
 def _run_tv_fb(log_obs, A, sb, st, log_p0, log_beta_T=None, posterior=False, out_mask=None):
@@ -843,10 +891,13 @@ class SparseLogLik(torch.autograd.Function):
 
         loglik = SparseLogLik.apply(log_obs, log_w, log_p0, transitions, lengths)
 
-    lengths: host int64 (B) from ops.ragged_lengths, or None."""
+    lengths: host int64 (B) from ops.ragged_lengths, or None.  range_guard (default on): a sequence
+    that left the kernels' fp32 range (range_guard.out_of_range) takes its value, posterior and arc
+    counts -- so its gradients -- from the float64 log-space loop; the others keep the kernels' bits.
+    One host read of a flag per forward; skipped while a CUDA graph is being captured."""
 
     @staticmethod
-    def forward(ctx, log_obs, log_w, log_p0, transitions, lengths=None):
+    def forward(ctx, log_obs, log_w, log_p0, transitions, lengths=None, range_guard=True):
         tr = transitions
         nat.require_gpu(log_obs, log_w, log_p0)
         obs = log_obs.detach().to(torch.float32).contiguous()
@@ -856,14 +907,24 @@ class SparseLogLik(torch.autograd.Function):
         loglik, post, ws = ops.sparse_forward_backward(
             obs, tr.in_ptr_host, tr.in_ptr, tr.in_src, w[tr.perm_in].contiguous(), tr.out_ptr_host, tr.out_ptr,
             tr.out_dst, w[tr.perm_out].contiguous(), log_p0.detach(), want_post, lengths)
-        ctx.transitions, ctx.lengths = tr, lengths
+        bad = rg.sparse_flagged(ws, obs, lengths) if range_guard and obs.shape[0] else None
+        if bad is not None:
+            lens = None if lengths is None else lengths.to(obs.device)[bad]
+            ll, g, _ = rg.logspace_forward_backward(obs[bad], log_p0, src=tr.src, dst=tr.dst, log_w=w, lengths=lens,
+                                                    want_xi=False)
+            loglik = loglik.index_copy(0, bad, ll.to(loglik.dtype))
+            if want_post:
+                post = post.index_copy(0, bad, g.to(post.dtype))
+        ctx.transitions, ctx.lengths, ctx.bad = tr, lengths, bad
         ctx.dtypes = (log_obs.dtype, log_w.dtype, log_p0.dtype)
-        ctx.save_for_backward(post if want_post else None, *((obs, w, ws) if need[1] else (None, None, None)))
+        # (log_p0: the backward's log-space counts of the flagged sequences need it)
+        ctx.save_for_backward(post if want_post else None, *((obs, w, ws) if need[1] else (None, None, None)),
+                              log_p0.detach() if bad is not None and need[1] else None)
         return loglik
 
     @staticmethod
     def backward(ctx, grad_loglik):
-        post, obs, w, ws = ctx.saved_tensors
+        post, obs, w, ws, l0 = ctx.saved_tensors
         need = ctx.needs_input_grad
         tr = ctx.transitions
         g = grad_loglik.to(torch.float32).contiguous()
@@ -873,5 +934,12 @@ class SparseLogLik(torch.autograd.Function):
         if need[2]:
             g_p0 = (post[:, 0] * g[:, None]).sum(0).to(ctx.dtypes[2])
         if need[1]:
-            g_w = ops.sparse_arc_counts(obs, tr.src, tr.dst, w.contiguous(), ws, g, ctx.lengths).to(ctx.dtypes[1])
-        return g_obs, g_w, g_p0, None, None
+            g_w = ops.sparse_arc_counts(obs, tr.src, tr.dst, w.contiguous(), ws, g, ctx.lengths)
+            bad = ctx.bad
+            if bad is not None:
+                # the forward neutralised the flagged sequences' rows: their counts come from the loop
+                lens = None if ctx.lengths is None else ctx.lengths.to(obs.device)[bad]
+                g_w = g_w + rg.logspace_forward_backward(obs[bad], l0, src=tr.src, dst=tr.dst, log_w=w,
+                                                         lengths=lens, weight=g[bad])[2]
+            g_w = g_w.to(ctx.dtypes[1])
+        return g_obs, g_w, g_p0, None, None, None

@@ -210,6 +210,22 @@ __device__ __forceinline__ void wave_argmax_dpp(float& v, int& i) {
   i = ic;
 }
 
+// Out of the fp32 range (hmm355.h, range contract) the chains can leave 0, denormals, inf and NaN
+// in their rows and log-scales.  What is formed from them afterwards -- the row passes' posterior,
+// forward and backward rows, the arc counts, the stored loglik -- must still be clean: a dead row
+// is all zero, a dead sequence's loglik -inf.  The tests below are on the bits, not float
+// compares: the library is built with -fno-honor-nans, under which a compare may be folded as
+// if no operand were NaN, and the device keeps denormals, so 1 / x of a positive x can be inf.
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+// 1 / x of a positive normal x (so finite, at most 2^126); 0 for 0, a denormal, a negative, inf or NaN
+__device__ __forceinline__ bool normal_bits(float x) { return (__float_as_uint(x) - 0x00800000u) < 0x7f000000u; }
+__device__ __forceinline__ float rcp_normal(float x) { return normal_bits(x) ? 1.f / x : 0.f; }
+__device__ __forceinline__ float clean_loglik(float x) { return finite_bits(x) ? x : -INFINITY; }
+// x where a row's factor `is` (rcp_normal of its sum) is alive and x is finite, else 0
+__device__ __forceinline__ float row_value(float x, float is) {
+  return (__float_as_uint(is) != 0u && finite_bits(x)) ? x : 0.f;
+}
+
 // all-lane wave sum / max on DPP + permlane swaps (no LDS round trips)
 __device__ __forceinline__ float wave_sum_dpp(float x) { return rows_sum(row16_sum(x)); }
 __device__ __forceinline__ float wave_max_dpp2(float x) {

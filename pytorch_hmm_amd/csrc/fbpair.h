@@ -122,22 +122,22 @@ __device__ __forceinline__ void fb_pair_dense(const PairArgs& p, float* lds, int
     }
     mu = wave_max(mu);
     mv = wave_max(mv);
-    const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+    const float iu = rcp_normal(mu), iv = rcp_normal(mv);  // (common.h: a dead row is all zero)
     float pp[K], s = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) { pp[k] = (u[k] * iu) * (v[k] * iv); s += pp[k]; }
     s = wave_sum(s);
-    const float is = s > 0.f ? 1.f / s : 0.f;
+    const float is = rcp_normal(s);
     const float la = p.fa.ls[row], lb = p.fb.ls[row];
     float lv = -INFINITY, lm;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = K * l + k;
-      const float fw = __expf(__logf(u[k]) + la);
+      const float fw = row_value(__expf(__logf(u[k]) + la), 1.f);
       if (j < N) {
-        if (p.mask & HMM355_FB_POSTERIOR) p.posterior[row * N + j] = pp[k] * is;
+        if (p.mask & HMM355_FB_POSTERIOR) p.posterior[row * N + j] = row_value(pp[k] * is, is);
         if (p.mask & HMM355_FB_FORWARD) p.forward[row * N + j] = fw;
-        if (p.mask & HMM355_FB_BACKWARD) p.backward[row * N + j] = __expf(__logf(v[k]) + lb);
+        if (p.mask & HMM355_FB_BACKWARD) p.backward[row * N + j] = row_value(__expf(__logf(v[k]) + lb), 1.f);
         lv = fmaxf(lv, __logf(fw + 1e-8f));
       }
     }
@@ -316,9 +316,10 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
       // exp(log x + LS) (the two-kernel path's bits); a row whose log-scale is below -110 is
       // exactly 0 (x <= N = 128 < e^5, and e^-105 is below the smallest fp32 denormal), as
       // the reference's exp(log alpha) underflows: a uniform branch skips the transcendentals
-      if (LS >= -110.f) {
+      // (common.h: a NaN log-scale or a NaN / inf entry gives zeros)
+      if (LS >= -110.f && finite_bits(LS)) {
 #pragma unroll
-        for (int kk = 0; kk < K; ++kk) o[q][kk] = __expf(__logf(x[q][kk]) + LS);
+        for (int kk = 0; kk < K; ++kk) o[q][kk] = row_value(__expf(__logf(x[q][kk]) + LS), 1.f);
       } else {
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) o[q][kk] = 0.f;
@@ -347,9 +348,10 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
       const float sw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ps[q]), 63));
-      const float is = sw > 0.f ? __builtin_amdgcn_rcpf(sw) : 0.f;
+      // (common.h: a row whose sum is not a positive normal number is a dead row, all zero)
+      const float is = normal_bits(sw) ? __builtin_amdgcn_rcpf(sw) : 0.f;
 #pragma unroll
-      for (int kk = 0; kk < K; ++kk) pp[q][kk] *= (kAbl & abl::kPairNoScale) ? 1.f : is;
+      for (int kk = 0; kk < K; ++kk) pp[q][kk] = (kAbl & abl::kPairNoScale) ? pp[q][kk] : row_value(pp[q][kk] * is, is);
       if (kAbl & (abl::kPairNoPostStores | abl::kPairNoStores)) continue;  // (diag: no posterior stores)
       if (full) {
         buf_store<K, kBufNT>(rP, poff[q], pp[q]);
@@ -367,7 +369,7 @@ __global__ void __launch_bounds__(PairL<NP>::NT) fb_pair_kernel(PairArgs p) {
         if (j0 + NH * q < 16 && 16 * k + j0 + NH * q == T - 1) {
           const float LS = (float)(base + (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xs), (j0 + NH * q) & 15)));
           // loglik = LS_{T-1} + log c_{T-1} (the chain left c_{T-1} = sum u_{T-1} in its ring)
-          if (p.fa.loglik && l == 0) p.fa.loglik[b] = LS + __logf(la[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]);
+          if (p.fa.loglik && l == 0) p.fa.loglik[b] = clean_loglik(LS + __logf(la[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
           if (p.lik_ref) {  // hmm.py:206: logsumexp_j log(forward_{T-1}[j] + 1e-8)
             float lv[K], mm = -INFINITY;
 #pragma unroll

@@ -34,14 +34,15 @@ __device__ __forceinline__ void post_row_lanes(const float (&u)[K], const float 
   for (int k = 0; k < K; ++k) { mu = fmaxf(mu, u[k]); mv = fmaxf(mv, v[k]); }
   mu = wave_max_dpp2(mu);
   mv = wave_max_dpp2(mv);
-  const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+  // (common.h: a row whose maxima or sum are not positive normal numbers is a dead row, all zero)
+  const float iu = rcp_normal(mu), iv = rcp_normal(mv);
   float p[K], sum = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) { p[k] = (u[k] * iu) * (v[k] * iv); sum += p[k]; }
   sum = wave_sum_dpp(sum);
-  const float is = sum > 0.f ? 1.f / sum : 0.f;
+  const float is = rcp_normal(sum);
 #pragma unroll
-  for (int k = 0; k < K; ++k) p[k] *= is;
+  for (int k = 0; k < K; ++k) p[k] = row_value(p[k] * is, is);
   if (!on) return;  // (wave-uniform: a row the caller computes but does not own)
   if (vec) {
     if constexpr (K == 1) dst[l] = p[0];
@@ -139,12 +140,12 @@ __global__ void __launch_bounds__(256) fb_posterior_kernel(PostArgs a) {
     for (int k = 0; k < K; ++k) { mu = fmaxf(mu, u[k]); mv = fmaxf(mv, v[k]); }
     mu = wave_max_dpp2(mu);
     mv = wave_max_dpp2(mv);
-    const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+    const float iu = rcp_normal(mu), iv = rcp_normal(mv);
     float p[K], s = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) { p[k] = (u[k] * iu) * (v[k] * iv); s += p[k]; }
     s = wave_sum_dpp(s);
-    const float is = s > 0.f ? 1.f / s : 0.f;
+    const float is = rcp_normal(s);
     const bool last = (row % a.T) == (size_t)(a.T - 1);
     // forward / backward only where they are stored (fb.hip's chains write them at flush
     // time) or the reference's likelihood needs the last forward row: the transcendentals
@@ -152,17 +153,18 @@ __global__ void __launch_bounds__(256) fb_posterior_kernel(PostArgs a) {
     float fw[K], bw[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      p[k] *= is;
+      p[k] = row_value(p[k] * is, is);
       fw[k] = 0.f;
       bw[k] = 0.f;
     }
+    // (a NaN or inf scaled entry or log-scale: 0, as a dead row's posterior)
     if ((a.mask & HMM355_FB_FORWARD) || (last && a.lik_ref)) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) fw[k] = __expf(__logf(u[k]) + la);
+      for (int k = 0; k < K; ++k) fw[k] = row_value(__expf(__logf(u[k]) + la), 1.f);
     }
     if (a.mask & HMM355_FB_BACKWARD) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) bw[k] = __expf(__logf(v[k]) + lb);
+      for (int k = 0; k < K; ++k) bw[k] = row_value(__expf(__logf(v[k]) + lb), 1.f);
     }
     if (vec) {
       VecK t;

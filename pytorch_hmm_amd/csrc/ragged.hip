@@ -314,7 +314,7 @@ __global__ void __launch_bounds__(256) rag_scan_kernel(RagPostArgs a) {
     a.LA[r0 + t] = 0.f;
     a.LB[r0 + t] = 0.f;
   }
-  if (tid == 0 && a.loglik) a.loglik[b] = (float)(ca + log((double)s_last));
+  if (tid == 0 && a.loglik) a.loglik[b] = clean_loglik((float)(ca + log((double)s_last)));
 }
 
 // One wave per (b,t) row, grid-stride: fb_posterior_kernel's arithmetic (post.h) on rows of
@@ -356,26 +356,27 @@ __global__ void __launch_bounds__(256) rag_post_kernel(RagPostArgs a) {
     for (int k = 0; k < K; ++k) { mu = fmaxf(mu, u[k]); mv = fmaxf(mv, v[k]); }
     mu = wave_max_dpp2(mu);
     mv = wave_max_dpp2(mv);
-    const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+    // (common.h: a row whose maxima or sum are not positive normal numbers is a dead row, all zero)
+    const float iu = rcp_normal(mu), iv = rcp_normal(mv);
     float p[K], s = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) { p[k] = (u[k] * iu) * (v[k] * iv); s += p[k]; }
     s = wave_sum_dpp(s);
-    const float is = s > 0.f ? 1.f / s : 0.f;
+    const float is = rcp_normal(s);
     float fw[K], bw[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      p[k] *= is;
+      p[k] = row_value(p[k] * is, is);
       fw[k] = 0.f;
       bw[k] = 0.f;
     }
     if ((a.mask & HMM355_FB_FORWARD) || (last && a.lik_ref)) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) fw[k] = __expf(__logf(u[k]) + la);
+      for (int k = 0; k < K; ++k) fw[k] = row_value(__expf(__logf(u[k]) + la), 1.f);
     }
     if (a.mask & HMM355_FB_BACKWARD) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) bw[k] = __expf(__logf(v[k]) + lb);
+      for (int k = 0; k < K; ++k) bw[k] = row_value(__expf(__logf(v[k]) + lb), 1.f);
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {

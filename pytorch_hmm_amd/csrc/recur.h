@@ -625,7 +625,8 @@ __device__ __forceinline__ void rec_flush(const RecArgs& a, const float* lds, in
     if constexpr (KIND != kVit && (WHAT & 2)) {
       if (a.out_exp) {
         const float ls = __shfl(lsv, row);
-        const bool live = ls >= -110.f;
+        // (common.h: a NaN log-scale or a NaN / inf entry of this lane's four gives zeros)
+        const bool live = ls >= -110.f && finite_bits(ls) && finite_bits((v.x + v.y) + (v.z + v.w));
         float ov[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) ov[k] = live ? __expf(__logf(ov[k]) + ls) : 0.f;
@@ -708,7 +709,7 @@ __device__ __forceinline__ void rec_keep_c_last(float* lds, int T, float ys) {
 // loglik = LS_{T-1} + log c_{T-1}, for the wave whose `base` has run through the last block
 template <int NP>
 __device__ __forceinline__ float rec_loglik(const float* lds, int T, double base) {
-  return (float)(base + (double)__logf(lds[RC<NP>::OFF_SC + 64 * ((T - 1) & (RC<NP>::RING - 1))]));
+  return clean_loglik((float)(base + (double)__logf(lds[RC<NP>::OFF_SC + 64 * ((T - 1) & (RC<NP>::RING - 1))])));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -906,7 +907,7 @@ __device__ __forceinline__ void rec_run_dpp(const RecArgs& a, float* lds, int b)
   rec_flush<NP, KIND>(a, lds, b, nblocks - 1, tid, rec_ls_scan<NP, KIND>(a, lds, b, nblocks - 1, base, w == C::NW - 1));
   if (KIND == kFbAlpha && a.loglik && tid == C::NT - 64) {
     // loglik = LS_{T-1} + log c_{T-1}; `base` (wave NW-1) now holds LS_{T-1}
-    a.loglik[b] = (float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
+    a.loglik[b] = clean_loglik((float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))])));
   }
 }
 
@@ -1028,7 +1029,7 @@ __device__ __forceinline__ void rec_rb_helper(const RecArgs& a, float* lds, int 
     publish(nblocks);
   }
   if (KIND == kFbAlpha && a.loglik && h == NH - 1 && l == 0) {
-    a.loglik[b] = (float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))]));
+    a.loglik[b] = clean_loglik((float)(base + (double)__logf(lds[C::OFF_SC + 64 * ((T - 1) & (C::RING - 1))])));
   }
 }
 

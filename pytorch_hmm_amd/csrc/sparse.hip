@@ -506,7 +506,7 @@ __global__ void __launch_bounds__(256) sp_scan_kernel(const float* __restrict__ 
       ts += part[k];
       tu += last[k];
     }
-    loglik[b] = (float)(ts + log(tu));
+    loglik[b] = clean_loglik((float)(ts + log(tu)));
   }
 }
 
@@ -533,21 +533,23 @@ __global__ void __launch_bounds__(256) sp_post_kernel(const float* __restrict__ 
       }
       mu = wave_max_dpp2(mu);
       mv = wave_max_dpp2(mv);
-      iu = mu > 0.f ? 1.f / mu : 0.f;
-      iv = mv > 0.f ? 1.f / mv : 0.f;
+      // (common.h: a row whose maxima or sum are not positive normal numbers is a dead row: zeros,
+      // and zero factors for the arc counts)
+      iu = rcp_normal(mu);
+      iv = rcp_normal(mv);
       float s = 0.f;
       for (int j = l; j < N; j += 64) s += (u[j] * iu) * (v[j] * iv);
       s = wave_sum_dpp(s);
-      is = s > 0.f ? 1.f / s : 0.f;
+      is = rcp_normal(s);
     }
     if (l == 0) {
-      Q1[row] = iu * is;
-      Q2[row] = iv;
+      Q1[row] = row_value(iu * is, is);
+      Q2[row] = row_value(iv, is);
     }
     if (posterior) {
       float* p = posterior + row * N;
-      if (is > 0.f) {
-        for (int j = l; j < N; j += 64) p[j] = ((u[j] * iu) * (v[j] * iv)) * is;
+      if (__float_as_uint(is) != 0u) {
+        for (int j = l; j < N; j += 64) p[j] = row_value(((u[j] * iu) * (v[j] * iv)) * is, is);
       } else {
         for (int j = l; j < N; j += 64) p[j] = 0.f;
       }
@@ -592,10 +594,10 @@ __global__ void __launch_bounds__(256) sp_count_kernel(SpCntArgs a) {
     const int b = (int)(r / T), t = (int)(r % T);
     if (t < 1 || t >= sp_len(a.lengths, b, T)) continue;
     const float ca = a.CA[r - 1];
-    const float ica = ca > 0.f ? 1.f / ca : 0.f;
+    const float ica = rcp_normal(ca);
     const float left = (a.U[(size_t)(r - 1) * N + sc] * ica) * A;
     const float right = (expf(a.obs[(size_t)r * N + dc] - a.rmax[r]) * a.V[(size_t)r * N + dc]) * a.Q2[r];
-    const float x = (left * right) * a.Q1[r];
+    const float x = row_value((left * right) * a.Q1[r], a.Q1[r]);  // (a dead frame has Q1 = 0: counts 0)
     const float gb = a.g ? a.g[b] : 1.f;
     acc += (double)x * (double)gb;
   }

@@ -745,7 +745,7 @@ __global__ void __launch_bounds__(64) tv_scan_kernel(const float* __restrict__ C
       if (t < T) LA[o + t] = (float)(base + x);
       base += __shfl(x, 63);
     }
-    if (l == 0 && loglik) loglik[b] = (float)(base + (double)__logf(CA[o]));
+    if (l == 0 && loglik) loglik[b] = clean_loglik((float)(base + (double)__logf(CA[o])));
   } else {
     double base = bscale ? (double)bscale[b] : 0.0;  // LB_{T-1} = log of the terminal vector's scale
     for (int t1 = T; t1 > 0; t1 -= 64) {

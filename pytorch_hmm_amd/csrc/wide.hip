@@ -423,7 +423,7 @@ __global__ void __launch_bounds__(256) wide_scan_kernel(WFbArgs a, double* __res
     }
     __syncthreads();
   }
-  if (tid == 0 && loglik) loglik[blockIdx.x] = (float)(ca + log((double)s_last));
+  if (tid == 0 && loglik) loglik[blockIdx.x] = clean_loglik((float)(ca + log((double)s_last)));
 }
 
 // One wave per (b,t) row, grid-stride: posterior = U V / sum(U V) (scale-invariant; each row
@@ -454,17 +454,17 @@ __global__ void __launch_bounds__(256) wide_post_kernel(WFbArgs a, const double*
       }
       mu = wave_max_dpp2(mu);
       mv = wave_max_dpp2(mv);
-      const float iu = mu > 0.f ? 1.f / mu : 0.f, iv = mv > 0.f ? 1.f / mv : 0.f;
+      const float iu = rcp_normal(mu), iv = rcp_normal(mv);  // (common.h: a dead row is all zero)
       float s = 0.f;
       for (int j = l; j < N; j += 64) s += (u[j] * iu) * (v[j] * iv);
       s = wave_sum_dpp(s);
-      const float is = s > 0.f ? 1.f / s : 0.f;
-      for (int j = l; j < N; j += 64) posterior[row * N + j] = (u[j] * iu) * (v[j] * iv) * is;
+      const float is = rcp_normal(s);
+      for (int j = l; j < N; j += 64) posterior[row * N + j] = row_value((u[j] * iu) * (v[j] * iv) * is, is);
     }
     if (mask & HMM355_FB_FORWARD)
-      for (int j = l; j < N; j += 64) forward[row * N + j] = __expf((float)((double)__logf(u[j]) + cla));
+      for (int j = l; j < N; j += 64) forward[row * N + j] = row_value(__expf((float)((double)__logf(u[j]) + cla)), 1.f);
     if (mask & HMM355_FB_BACKWARD)
-      for (int j = l; j < N; j += 64) backward[row * N + j] = __expf((float)((double)__logf(v[j]) + clb));
+      for (int j = l; j < N; j += 64) backward[row * N + j] = row_value(__expf((float)((double)__logf(v[j]) + clb)), 1.f);
     if (last && lik_ref) {
       float m = -INFINITY;
       for (int j = l; j < N; j += 64) m = fmaxf(m, __logf(__expf((float)((double)__logf(u[j]) + cla)) + 1e-8f));

@@ -22,9 +22,10 @@ from torch import Tensor
 
 from . import _native as nat
 from . import ops
+from . import range_guard as rg
 from .autograd import _require_narrow, _run_fb, _staged_emissions, valid_frames
 
-__all__ = ["EStats", "e_step", "transition_m_step", "gaussian_m_step"]
+__all__ = ["EStats", "e_step", "sequence_loglik", "transition_m_step", "gaussian_m_step"]
 
 
 @dataclass
@@ -49,11 +50,20 @@ class EStats:
                       self.n_seq + other.n_seq)
 
 
-def e_step(log_emis: Tensor, log_P: Tensor, log_p0: Tensor, lengths=None, plan: Optional[Tensor] = None) -> EStats:
+def e_step(log_emis: Tensor, log_P: Tensor, log_p0: Tensor, lengths=None, plan: Optional[Tensor] = None,
+           range_guard: bool = True) -> EStats:
     """Posteriors and expected counts of the chain for log-emissions log_emis (B,T,N), log_P (N,N)
     (-inf for a forbidden transition: xi is exactly 0 there) and log_p0 (N); lengths as
     ops.ragged_lengths (frames past a length are never read).  One forward-backward call, no
-    autograd.  N <= 256."""
+    autograd.  N <= 256.
+
+    range_guard (default on): the sequences that left the kernels' fp32 range
+    (range_guard.out_of_range over the rows the call leaves: possible only with exact zeros in
+    log_P) are recomputed in float64 log space (range_guard.logspace_forward_backward) and their
+    loglik, gamma and share of xi / gamma0 replaced; every other sequence keeps the kernels' bits.
+    This costs one host read of a flag per call, and nothing else while no sequence is flagged.  It
+    is skipped while a CUDA graph is being captured.  Callers whose tables are floored by
+    construction (log(P + 1e-8)) pass False."""
     if log_emis.dim() != 3:
         raise ValueError(f"log_emis must be (B, T, N); got {tuple(log_emis.shape)}")
     B, T, N = log_emis.shape
@@ -70,14 +80,14 @@ def e_step(log_emis: Tensor, log_P: Tensor, log_p0: Tensor, lengths=None, plan: 
         if B == 0:
             return EStats(torch.zeros(0, device=dev), torch.zeros(0, T, N, device=dev), torch.zeros(N, N, device=dev),
                           torch.zeros(N, device=dev), 0)
-        post, loglik, _, U, V, _, _, CA, _ = _run_fb(obs, lP, l0, nat.OBS_LOG, posterior=True,
+        post, loglik, _, U, V, _, _, CA, CB = _run_fb(obs, lP, l0, nat.OBS_LOG, posterior=True,
                                                       plan=None if lens is not None else plan, lengths=lens)
-        gamma0 = post[:, 0].sum(0)
+        valid = valid_frames(lens, T, dev)
+        e = _staged_emissions(obs, nat.OBS_LOG, valid) if T > 1 or range_guard else None
+        bad = rg.flagged(U, V, CA, lens, E=e, CB=CB) if range_guard else None
         xi = torch.zeros(N, N, device=dev)
         if T > 1:
             # SequenceLogLik.backward's X (x) Y with G = 1 (the terminal backward vector is 1)
-            valid = valid_frames(lens, T, dev)
-            e = _staged_emissions(obs, nat.OBS_LOG, valid)
             S = (U * V).sum(-1)
             den = (CA[:, :-1] * S[:, 1:]).unsqueeze(-1)
             if valid is None:
@@ -87,8 +97,40 @@ def e_step(log_emis: Tensor, log_P: Tensor, log_p0: Tensor, lengths=None, plan: 
                 X = torch.where(pair, U[:, :-1] / torch.where(pair, den, torch.ones_like(den)),
                                 torch.zeros_like(U[:, :-1]))
             Y = e[:, 1:] * V[:, 1:]
+            if bad is not None:
+                # the flagged sequences' rows may hold anything (NaN included): out of both factors
+                X, Y = X.index_fill(0, bad, 0.0), Y.index_fill(0, bad, 0.0)
             xi = torch.exp(lP) * torch.einsum("bti,btj->ij", X, Y)
+        if bad is not None:
+            ll, g, x = rg.logspace_forward_backward(obs[bad], l0, lP, lengths=None if lens is None else lens.to(dev)[bad])
+            loglik = loglik.index_copy(0, bad, ll.to(loglik.dtype))
+            post = post.index_copy(0, bad, g.to(post.dtype))
+            xi = xi + x.to(xi.dtype)
+        gamma0 = post[:, 0].sum(0)
     return EStats(loglik, post, xi, gamma0, B)
+
+
+def sequence_loglik(log_emis: Tensor, log_P: Tensor, log_p0: Tensor, lens: Optional[Tensor] = None,
+                    range_guard: bool = True) -> Tensor:
+    """(B,) exact log-likelihoods for log-emissions (B,T,N), without posteriors or autograd: the
+    likelihood half of e_step, with its guard (a sequence range_guard.out_of_range flags over the
+    rows the call leaves takes its value from the float64 log-space loop; the others keep the
+    kernels' bits).  lens: active lengths (ops.active_lengths) or None.  Above 256 states the
+    batch-tiled form runs, which leaves no such rows: unguarded there, in range only (hmm355.h)."""
+    B, T, N = log_emis.shape
+    with torch.no_grad():
+        obs, lP, l0 = (t.detach().to(torch.float32).contiguous() for t in (log_emis, log_P, log_p0))
+        if N > nat.NARROW_MAX_STATES or B == 0:
+            return ops.forward_backward(obs, lP, l0, nat.OBS_LOG, 0)[3]
+        _, loglik, _, U, V, _, _, CA, CB = _run_fb(obs, lP, l0, nat.OBS_LOG, lengths=lens)
+        if range_guard:
+            e = _staged_emissions(obs, nat.OBS_LOG, valid_frames(lens, T, obs.device))
+            bad = rg.flagged(U, V, CA, lens, E=e, CB=CB)
+            if bad is not None:
+                ll, _, _ = rg.logspace_forward_backward(obs[bad], l0, lP, want_xi=False,
+                                                        lengths=None if lens is None else lens.to(obs.device)[bad])
+                loglik = loglik.index_copy(0, bad, ll.to(loglik.dtype))
+    return loglik
 
 
 def transition_m_step(xi: Tensor, gamma0: Tensor, n_seq: int, old_P: Tensor, old_p0: Tensor,
@@ -182,18 +224,20 @@ def check_batch(x, lengths, D: int, N: int):
     return x, lens, frames
 
 
-def accumulate(batches, D, N, score, stats, log_P, log_p0, plan=None, want_stats=True):
+def accumulate(batches, D, N, score, stats, log_P, log_p0, plan=None, want_stats=True, range_guard=True):
     """The E-step over `batches`: score(x) -> log-emissions (B,T,N), stats(x, gamma, lens) -> (occ,
     sx, sxx).  Returns (EStats summed, [occ, sx, sxx] summed or None, frames).  Padded frames of x
     are zeroed (selected) before they are scored; the chain and the statistics kernel never read
-    them."""
+    them.  range_guard as e_step's: on for the layers' em_step / fit, whose tables may hold exact
+    zeros (a fixed transition_matrix) and whose Gaussian log-densities differ by hundreds of nats
+    between states (MixtureGaussianHMMLayer.log_likelihood goes through sequence_loglik)."""
     checked = [check_batch(x, lens, D, N) for x, lens in batches]
     total, sums, frames = None, None, 0
     for x, lens, nf in checked:
         if lens is not None:
             valid = valid_frames(lens, x.shape[1], x.device)
             x = torch.where(valid[..., None], x, torch.zeros_like(x))
-        es = e_step(score(x), log_P, log_p0, lens, plan)
+        es = e_step(score(x), log_P, log_p0, lens, plan, range_guard)
         if want_stats:
             part = stats(x, es.gamma, lens)
             sums = list(part) if sums is None else [a + b for a, b in zip(sums, part)]

@@ -260,7 +260,9 @@ class HMMPyTorch(HMM):
         nat.require_gpu(obs)
         log_P, log_p0, plan = self._device_params(obs.device)
         with torch.no_grad():
-            es = em.e_step(torch.log(obs.detach() + 1e-8), log_P.detach(), log_p0.detach(), lengths, plan)
+            # log(P + 1e-8) and log(obs + 1e-8) are floored by construction: in the kernels' range
+            es = em.e_step(torch.log(obs.detach() + 1e-8), log_P.detach(), log_p0.detach(), lengths, plan,
+                           range_guard=False)
             P, p0 = em.transition_m_step(es.xi, es.gamma0, es.n_seq, self.P.detach().to(obs.device),
                                          self.p0.detach().to(obs.device))
         return P, p0, es.loglik

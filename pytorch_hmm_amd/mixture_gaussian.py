@@ -366,9 +366,11 @@ class MixtureGaussianHMMLayer(nn.Module):
         batches = em.as_batches(observations, lengths)
         return em.run_fit(lambda: self._em_iteration(batches, self._EM_UPDATES, 1e-4), n_iter, tol)
 
-    def log_likelihood(self, observations: torch.Tensor, lengths=None) -> torch.Tensor:
+    def log_likelihood(self, observations: torch.Tensor, lengths=None, range_guard: bool = True) -> torch.Tensor:
         """(B,) exact log-likelihood log p(x_b) of each sequence under the model em_step
-        re-estimates (mixture emissions, log_softmax transitions, uniform start).  No gradients."""
+        re-estimates (mixture emissions, log_softmax transitions, uniform start).  No gradients.
+        range_guard as em.e_step's (em.sequence_loglik): a fixed transition_matrix may hold exact
+        zeros and the mixture log-densities differ by hundreds of nats between states."""
         from . import em
         self._em_check()
         x, lens, _ = em.check_batch(observations, lengths, self.feature_dim, self.num_states)
@@ -378,9 +380,7 @@ class MixtureGaussianHMMLayer(nn.Module):
                 valid = valid_frames(lens, x.shape[1], x.device)
                 x = torch.where(valid[..., None], x, torch.zeros_like(x))
             lp = ops.gmm_diag_logprob(x, self.means.detach(), self._component_log_vars().detach(), log_w, 1)
-            if lens is not None:
-                return ops.forward_backward_ragged(lp, log_P, log_p0, ops.OBS_LOG, lens, 0)[3]
-            return ops.forward_backward(lp, log_P, log_p0, ops.OBS_LOG, 0)[3]
+            return em.sequence_loglik(lp, log_P, log_p0, lens, range_guard)
 
     def get_model_info(self) -> dict:
         total = sum(p.numel() for p in self.parameters())

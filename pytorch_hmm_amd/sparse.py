@@ -13,6 +13,7 @@ import torch
 from torch import Tensor, nn
 
 from . import ops
+from . import range_guard as rg
 from .autograd import SparseLogLik
 
 MAX_STATES = ops.SPARSE_MAX_STATES
@@ -128,9 +129,16 @@ def sparse_viterbi(transitions: SparseTransitions, log_obs: Tensor, log_p0: Tens
 
 def sparse_e_step(transitions: SparseTransitions, log_obs: Tensor, log_p0: Tensor, log_w: Optional[Tensor] = None,
                   lengths=None, weight: Optional[Tensor] = None, want_posterior: bool = True,
-                  want_counts: bool = True) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+                  want_counts: bool = True, range_guard: bool = True
+                  ) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
     """(loglik (B), gamma (B,T,N) or None, xi (E) fp64 in the caller's arc order or None): one
-    forward-backward call and, for xi, one arc-count call over the rows it leaves."""
+    forward-backward call and, for xi, one arc-count call over the rows it leaves.
+
+    range_guard (default on): the sequences that left the kernels' fp32 range
+    (range_guard.out_of_range over the workspace's rows -- an arc list is a table of exact zeros,
+    where that can happen) are recomputed in float64 log space and their loglik, gamma and share
+    of xi replaced; the others keep the kernels' bits.  One host read of a flag per call; skipped
+    while a CUDA graph is being captured."""
     tr = transitions
     w = (tr.log_w if log_w is None else log_w).detach().to(torch.float32)
     host = None if lengths is None else ops.ragged_lengths(lengths, log_obs.shape[0], log_obs.shape[1])
@@ -138,10 +146,20 @@ def sparse_e_step(transitions: SparseTransitions, log_obs: Tensor, log_p0: Tenso
     loglik, post, ws = ops.sparse_forward_backward(obs, tr.in_ptr_host, tr.in_ptr, tr.in_src, w[tr.perm_in],
                                                    tr.out_ptr_host, tr.out_ptr, tr.out_dst, w[tr.perm_out], log_p0,
                                                    want_posterior, host)
+    bad = rg.sparse_flagged(ws, obs, host) if range_guard and obs.shape[0] else None
     xi = None
     if want_counts:
         # the destination order: neighbouring threads read neighbouring states
         xi = ops.sparse_arc_counts(obs, tr.in_src, tr.in_dst, w[tr.perm_in], ws, weight, host)[tr.inv_in]
+    if bad is not None:
+        ll, g, x = rg.logspace_forward_backward(obs[bad], log_p0, src=tr.src, dst=tr.dst, log_w=w,
+                                                lengths=None if host is None else host.to(obs.device)[bad],
+                                                weight=None if weight is None else weight[bad], want_xi=want_counts)
+        loglik = loglik.index_copy(0, bad, ll.to(loglik.dtype))
+        if want_posterior:
+            post = post.index_copy(0, bad, g.to(post.dtype))
+        if want_counts:
+            xi = xi + x
     return loglik, (post if want_posterior else None), xi
 
 
