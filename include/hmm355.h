@@ -10,6 +10,9 @@
  * Conventions (all entry points)
  *   - Plain device pointers and sizes; no framework types.  Every buffer is caller-owned
  *     device memory (hipMalloc / torch allocator); the library allocates nothing.
+ *   - Output and workspace buffers may hold anything on entry: every entry point writes each
+ *     byte of its workspace and outputs before it reads it, and writes every element of every
+ *     output it was asked for (tests/test_gpu_poison.py).
  *   - Dense row-major fp32, (B, T, N) = batch, time, states; states int64 (B, T).
  *   - `stream` is a hipStream_t (NULL = legacy default stream).  Launches are
  *     stream-ordered and asynchronous; there is no host synchronisation and no global
@@ -690,7 +693,8 @@ int hmm355_tv_viterbi_f32(const float* log_obs, const float* log_A, long long a_
  *   transition_logits) + 1e-8) (self-transitions are excluded by the recursion);
  *   dur_lp (S,Dmax) = DurationModel log-probabilities for d = 1..Dmax.
  * Viterbi outputs: segments right-aligned in (B,T) int64 seg_states / seg_durs, the last
- *   seg_count[b] entries of row b in time order; scores (B) = best final delta.  Candidate
+ *   seg_count[b] entries of row b in time order, the T - seg_count[b] entries in front of them
+ *   seg_states = -1 and seg_durs = 0; scores (B) = best final delta.  Candidate
  *   order (s' outer, d' inner, strict >) and fp32 addition order ((prev + logT) then
  *   (best + obs) + dur) are the reference's, so segmentations are bit-identical given
  *   identical fp32 quad/table inputs.
@@ -746,7 +750,9 @@ int hmm355_semimarkov_forward_ex_f32(const float* quad, const float* seg_const,
  *   expansions by score descending, ties by expansion index h*N + j ascending (Python's
  *   stable sort), score = (score_h + log_T[last_h][j]) + emis[t][j] in fp32.
  *   parent / hstate (B,T,K) int16: new hypothesis r at step t came from hypothesis
- *   parent[t][r] of step t-1 and entered state hstate[t][r].  states (B,T) int64: the best
+ *   parent[t][r] of step t-1 and entered state hstate[t][r]; while the beam is under-full (a step
+ *   has kn = min(K, live * N) < K hypotheses) the ranks r >= kn get parent = hstate = -1.
+ *   states (B,T) int64: the best
  *   hypothesis' last T states.  1 <= K <= 32 and live_max (<= 32) bounds every hyp_count[b];
  *   for N > 128, K and live_max <= 16 (else HMM355_E_ARG).
  * ------------------------------------------------------------------------------ */

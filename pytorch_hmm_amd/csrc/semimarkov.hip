@@ -343,6 +343,11 @@ __global__ void __launch_bounds__(64) smk_backtrace_kernel(SmArgs a) {
     cd = nd;
   }
   if (l == 0) a.seg_count[b] = k;
+  // the entries in front of the right-aligned segments: state -1, duration 0 (k is wave-uniform)
+  for (int i = l; i < T - k; i += 64) {
+    a.seg_states[(size_t)b * T + i] = -1;
+    a.seg_durs[(size_t)b * T + i] = 0;
+  }
 }
 
 // ---------------------------------------------------------------- the general form
@@ -582,6 +587,11 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
       __syncthreads();
     }
     if (tid == 0) a.seg_count[b] = k;
+    // the entries in front of the segments, as smk_backtrace_kernel: state -1, duration 0
+    for (int i = tid; i < T - k; i += kSwNT) {
+      a.seg_states[(size_t)b * T + i] = -1;
+      a.seg_durs[(size_t)b * T + i] = 0;
+    }
   }
 }
 

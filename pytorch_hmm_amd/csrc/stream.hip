@@ -191,6 +191,11 @@ __global__ void __launch_bounds__(256) stream_beam_kernel(BeamArgs a) {
             if (rr == lane) { lv = nl[rr]; pv = np[rr]; }
           a.parent[o] = (int16_t)pv;
           a.hstate[o] = (int16_t)lv;
+        } else if (lane < K) {
+          // an under-full beam (kn < K): the ranks that do not exist get parent = state = -1
+          const size_t o = ((size_t)b * T + t) * K + lane;
+          a.parent[o] = (int16_t)-1;
+          a.hstate[o] = (int16_t)-1;
         }
 #pragma unroll
         for (int h = 0; h < KM; ++h) { hs[h] = ns[h]; hl[h] = nl[h]; }

@@ -982,7 +982,8 @@ def _smk_forward_outputs(mk, B, T, S, Dm, want_alpha):
 @torch.library.custom_op("hmm355::semimarkov_viterbi", mutates_args=())
 def semimarkov_viterbi(quad: Tensor, seg_const: Optional[Tensor], log_init: Tensor, log_T: Tensor,
                        dur_lp: Tensor, flags: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """-> seg_states (B,T) int64, seg_durs (B,T) int64 (right-aligned), seg_count (B) int32,
+    """-> seg_states (B,T) int64, seg_durs (B,T) int64 (right-aligned: the last seg_count[b] entries
+    of row b; the entries in front of them are seg_states = -1, seg_durs = 0), seg_count (B) int32,
     scores (B).  flags: FORM_GENERAL forces the general form (identical results)."""
     quad, seg_const, log_init, log_T, dur_lp, B, T, S, Dm = _smk_args(quad, seg_const, log_init, log_T, dur_lp)
     dev = quad.device
@@ -1060,7 +1061,8 @@ def stream_beam(emis: Tensor, log_T: Tensor, beam_width: int, hyp_score: Tensor,
     updated IN PLACE; K = beam_width <= 32 (<= 16 when N > 128), N <= 256;
     first (B) int32 marks streams whose paths are still empty; live_max bounds hyp_count.  Returns (best-path states
     (B,T) int64, parent (B,T,K) int16, state (B,T,K) int16): new hypothesis r at step t came
-    from hypothesis parent[t, r] of step t-1 and entered state[t, r]."""
+    from hypothesis parent[t, r] of step t-1 and entered state[t, r]; at a step with fewer than K
+    hypotheses (an under-full beam: min(K, live * N) of them) the other ranks get parent = state = -1."""
     nat.require_gpu(emis, log_T, hyp_score, hyp_last, hyp_count, first)
     emis, log_T = _f32c(emis), _f32c(log_T)
     B, T, N = emis.shape

@@ -48,6 +48,8 @@ def gpu_viterbi(q, cs, li, lT, du, flags=0):
     ss, sd, cnt, sc = ops.semimarkov_viterbi(t(q), None if cs is None else t(cs), t(li), t(lT), t(du), flags)
     T = q.shape[1]
     ss, sd, cnt, sc = ss.cpu().numpy(), sd.cpu().numpy(), cnt.cpu().numpy(), sc.cpu().numpy()
+    for b in range(q.shape[0]):   # in front of the right-aligned segments: state -1, duration 0 (hmm355.h)
+        assert (ss[b, :T - cnt[b]] == -1).all() and (sd[b, :T - cnt[b]] == 0).all(), (b, cnt[b])
     return [(ss[b, T - cnt[b]:], sd[b, T - cnt[b]:], sc[b]) for b in range(q.shape[0])]
 
 

@@ -107,6 +107,24 @@ def test_kernels_vs_oracle_random(seed, B, T, N, K, ties, k0):
         assert np.array_equal(gpar[:, :k], opar[:, :k]) and np.array_equal(ghst[:, :k], ohst[:, :k])
 
 
+def test_under_full_beam_marks_missing_ranks():
+    """One live hypothesis, N = 2, K = 5: the steps have 2, 4, 5, 5 hypotheses.  The ranks a step
+    does not have get parent = state = -1 (hmm355.h); the others are the oracle's."""
+    rng = np.random.default_rng(13)
+    N, K, T = 2, 5, 4
+    emis = np.log(rng.dirichlet(np.ones(N), size=(1, T))).astype(np.float32)
+    log_T = np.log(rng.dirichlet(np.ones(N), size=N)).astype(np.float32)
+    hs, hl = [np.array([-0.5], np.float32)], [np.array([1])]
+    for _ in range(2):   # the second call's outputs reuse the first's blocks
+        (ghs, ghl, gpar, ghst, gst), = gpu_beam(emis, log_T, K, hs, hl, [True])
+        ohs, ohl, opar, ohst = O.c_stream_beam(emis[0], log_T, K, hs[0], hl[0], True)
+        assert np.array_equal(ghs, ohs) and np.array_equal(ghl, ohl) and len(ohs) == K
+        for step, kn in enumerate((2, 4, 5, 5)):
+            assert np.array_equal(gpar[step, :kn], opar[step, :kn]) and np.array_equal(ghst[step, :kn], ohst[step, :kn])
+            assert (gpar[step, :kn] >= 0).all() and (ghst[step, :kn] >= 0).all()
+            assert (gpar[step, kn:] == -1).all() and (ghst[step, kn:] == -1).all()
+
+
 def load_proc(g, beam):
     N, D, K, cs, md, la = (int(v) for v in g["config"][:6])
     p = StreamingHMMProcessor(N, D, chunk_size=cs, lookahead_frames=la, max_delay_frames=md,
