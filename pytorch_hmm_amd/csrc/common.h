@@ -20,6 +20,16 @@
 #define HMM355_STAMP 0
 #endif
 
+// HMM355_RED_FORM: the form of the banded chains' wave reduction (recur.h wave_red_level, namespace
+// red: 0 six dependent DPP levels, 1 the quad_perm pair as three row_shr of one register, 2 the
+// row_ror pair likewise, 3 both).  Not defined in the product build: recur.h then takes the form
+// each chain measured fastest with (red_form: HMM355_RED_FORM_ALPHA / _BETA / _VIT); defined, it
+// sets all three chains, for diagnostic builds.  HMM355_RED_PROBE (diagnostic builds,
+// tools/probe_wave_reduce.py): exports a kernel that runs every form on caller-given vectors.
+#ifndef HMM355_RED_PROBE
+#define HMM355_RED_PROBE 0
+#endif
+
 // HMM355_FABL: ablation knobs of the work beside the chains (csrc/follow.h), diagnostic builds
 // only; the bits are named in namespace fabl below.
 #ifndef HMM355_FBR

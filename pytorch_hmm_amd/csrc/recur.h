@@ -38,7 +38,7 @@ typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned 
 
 // How many steps ahead the banded chain wave (band_chain) reads a step's staged emission row
 // inside an unrolled 16-step block, by chain: 1 or 2.  Two for beta and Viterbi, whose reduction
-// is filled (wave_red_fill): the wait for a row read two steps ahead stands in gap kEmisWaitGap
+// is filled (wave_red_fill): the wait for a row read two steps ahead stands in gap emis_wait_gap
 // of the step in between, in the place of a wait state, and the step loses the issue slot the
 // s_waitcnt took ahead of the row's first use.  alpha leaves its placing to the compiler and
 // measured slower at two.  The macros are for diagnostic builds.
@@ -52,14 +52,32 @@ typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned 
 #define HMM355_EMIS_AHEAD_VIT 2
 #endif
 // the gap of the filled reduction (wave_red_fill) that holds the wait for a row read two steps
-// ahead: 4, ahead of row_bcast:15, which the register windows of up to two states a lane (NP <= 128)
-// leave empty (fill_cnt); where the step's own units fill it the wait costs there what it saved
-#ifndef HMM355_EMIS_WAIT_GAP
-#define HMM355_EMIS_WAIT_GAP 4
-#endif
-constexpr int kEmisWaitGap = HMM355_EMIS_WAIT_GAP;
+// ahead (emis_wait_gap below): in form 0 gap 4, ahead of row_bcast:15; in the forms with fewer
+// gaps the one ahead of row_bcast:31.  The register windows of up to two states a lane (NP <= 128)
+// leave it empty (fill_cnt); where the step's own units fill it the wait costs there what it
+// saved.  HMM355_EMIS_WAIT_GAP: diagnostic builds, the gap by number.
 constexpr int emis_ahead(int kind) {
   return kind == kFbAlpha ? HMM355_EMIS_AHEAD_ALPHA : kind == kFbBeta ? HMM355_EMIS_AHEAD_BETA : HMM355_EMIS_AHEAD_VIT;
+}
+// The form of the step's wave reduction (wave_red_level) by chain: what measured faster per chain
+// (DESIGN section 14 round 11): beta and Viterbi both triples, alpha, whose reduction is not
+// filled, the first one.  HMM355_RED_FORM (common.h) sets all three, for diagnostic builds.
+#ifdef HMM355_RED_FORM
+#define HMM355_RED_FORM_ALPHA HMM355_RED_FORM
+#define HMM355_RED_FORM_BETA HMM355_RED_FORM
+#define HMM355_RED_FORM_VIT HMM355_RED_FORM
+#endif
+#ifndef HMM355_RED_FORM_ALPHA
+#define HMM355_RED_FORM_ALPHA 1
+#endif
+#ifndef HMM355_RED_FORM_BETA
+#define HMM355_RED_FORM_BETA 3
+#endif
+#ifndef HMM355_RED_FORM_VIT
+#define HMM355_RED_FORM_VIT 3
+#endif
+constexpr int red_form(int kind) {
+  return kind == kFbAlpha ? HMM355_RED_FORM_ALPHA : kind == kFbBeta ? HMM355_RED_FORM_BETA : HMM355_RED_FORM_VIT;
 }
 
 // diagnostic builds (HMM355_STAMP=1): per wave [gather, compute, write-wait, barrier, steps,
@@ -119,24 +137,85 @@ constexpr int kFbNT = kRbHelpers<NP>::NT;
 // row (row 0; rows 0, 1) combines with 0 and holds a value nobody reads.  The result is taken
 // from lane 63 alone, and the lanes it descends from (lane 31 after row_bcast:15, lane 63)
 // always have a source: ((r3 + r2) + (r1 + r0)), as with the row masks 0xa / 0xc.
-template <bool MAX, int L>
-__device__ __forceinline__ float wave_red_level(float x) {
-  constexpr int CTRL = L == 0 ? 0xB1 : L == 1 ? 0x4E : L == 2 ? 0x124 : L == 3 ? 0x128 : L == 4 ? 0x142 : 0x143;
+//
+// The forms F of the reduction (HMM355_RED_FORM, a set of the bits red::kA and red::kB; 0 is the
+// six levels above).  The two wait states belong to the register a level reads THROUGH DPP; its
+// other operand is forwarded like any VALU operand.  So a pair of dependent levels becomes three
+// shifts of one settled register into a fresh accumulator, which wait once, for that register:
+//   kA  t = op(x, x >> 1); t = op(t, x >> 2); t = op(t, x >> 3)     in the place of the quad_perms
+//   kB  r = op(t, t >> 4); r = op(r, t >> 8); r = op(r, t >> 12)    in the place of the row_rors
+// (row_shr with bound_ctrl).  Lane 15 of each row ends with the row's 16 values, all of them from
+// inside the row; the lanes that shifted a 0 in are never among the sources of lane 15, and the
+// row_bcast levels read lanes 15, 31, 47 and 63 only.  A sum associates (((x15 + x14) + x13) + x12)
+// ... where form 0 has ((x0 + x1) + (x2 + x3)) ...; a maximum is the same bits in every form.
+// The hazard recognizer pads a DPP instruction for ANY operand a VALU instruction of the
+// compiler's wrote less than two slots ago, not only the shifted one, so the second and third
+// shift of a triple are one asm statement, inside which nothing is padded.  The first shift is the
+// compiler's own: it is padded for the triple's source by what the fillers ahead of it leave, and
+// once it may read the source the two behind it may.  The compiler takes the statement's result
+// for a VALU write, so it pads the level behind the triple as it pads any other.
+namespace red {
+constexpr int kA = 1, kB = 2;
+// the stages (a level or a triple) of form F, and the form-0 level stage S stands in the place of
+constexpr int stages(int F) { return 6 - (F & kA ? 1 : 0) - (F & kB ? 1 : 0); }
+constexpr bool triple_at(int F, int L) { return (L == 0 && (F & kA)) || (L == 2 && (F & kB)); }
+constexpr int level(int F, int S) {
+  int L = 0;
+  for (int s = 0; s < S; ++s) L += triple_at(F, L) ? 2 : 1;
+  return L;
+}
+}  // namespace red
+// op(acc, src >> SHR within the row), the compiler's instruction
+template <bool MAX, int SHR>
+__device__ __forceinline__ float red_shr(float acc, float src) {
   const float o = __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, L >= 4));
-  return MAX ? fmaxf(x, o) : x + o;
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), 0x110 + SHR, 0xF, 0xF, true));
+  return MAX ? fmaxf(acc, o) : acc + o;
+}
+// acc = op(op(acc, src >> S2), src >> S3), unpadded: src is settled, acc is no DPP source.
+// PIN (wave_red_fill): a volatile statement, which keeps its place among the sched_barriers as
+// fill_pin keeps a level's -- an empty asm behind this one would cost the one-state pad the
+// compiler puts between an asm statement's result and its first reader.
+#define HMM355_RED_SHR2(VOL, OP)                                                            \
+  asm VOL(OP " %0, %1, %0 row_shr:%2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"           \
+          OP " %0, %1, %0 row_shr:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"               \
+          : "+v"(acc) : "v"(src), "n"(S2), "n"(S3))
+template <bool MAX, int S2, int S3, bool PIN>
+__device__ __forceinline__ float red_shr2_asm(float acc, float src) {
+  if constexpr (MAX && PIN) HMM355_RED_SHR2(volatile, "v_max_f32_dpp");
+  else if constexpr (MAX) HMM355_RED_SHR2(, "v_max_f32_dpp");
+  else if constexpr (PIN) HMM355_RED_SHR2(volatile, "v_add_f32_dpp");
+  else HMM355_RED_SHR2(, "v_add_f32_dpp");
+  return acc;
+}
+#undef HMM355_RED_SHR2
+// stage S of form F (form 0: level S)
+template <bool MAX, int S, int F = 0, bool PIN = false>
+__device__ __forceinline__ float wave_red_level(float x) {
+  constexpr int L = red::level(F, S);
+  if constexpr (red::triple_at(F, L)) {
+    constexpr int K = L == 0 ? 1 : 4;
+    return red_shr2_asm<MAX, 2 * K, 3 * K, PIN>(red_shr<MAX, K>(x, x), x);
+  } else {
+    constexpr int CTRL = L == 0 ? 0xB1 : L == 1 ? 0x4E : L == 2 ? 0x124 : L == 3 ? 0x128 : L == 4 ? 0x142 : 0x143;
+    const float o = __builtin_bit_cast(
+        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, L >= 4));
+    return MAX ? fmaxf(x, o) : x + o;
+  }
 }
 __device__ __forceinline__ float wave_lane63(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
 }
 
 // Sum / max over all 64 lanes with DPP only, read from lane 63: wave-uniform.
+template <int F = 0>
 __device__ __forceinline__ float wave_sum_bcast(float x) {
-  static_for<0, 6>([&](auto L) { x = wave_red_level<false, decltype(L)::value>(x); });
+  static_for<0, red::stages(F)>([&](auto S) { x = wave_red_level<false, decltype(S)::value, F>(x); });
   return wave_lane63(x);
 }
+template <int F = 0>
 __device__ __forceinline__ float wave_max_bcast(float x) {
-  static_for<0, 6>([&](auto L) { x = wave_red_level<true, decltype(L)::value>(x); });
+  static_for<0, red::stages(F)>([&](auto S) { x = wave_red_level<true, decltype(S)::value, F>(x); });
   return wave_lane63(x);
 }
 
@@ -144,54 +223,85 @@ __device__ __forceinline__ float wave_max_bcast(float x) {
 // dependent levels waits two issue slots for the one before it, v_readlane one for the last
 // level, and the first VALU read of the SGPR two for v_readlane.  fill(integral_constant<G>)
 // is called in gap G and issues instructions of the caller's that do not read the reduction:
-// G = 0..5 ahead of level G, 6 ahead of v_readlane, 7 behind it (kFillSlots slots each).
+// G = 0..5 ahead of level G, 6 ahead of v_readlane, 7 behind it (fill_slots slots each); in form
+// F, ahead of each of its red::stages(F) stages (a triple waits once, ahead of its first shift:
+// 9 instructions and 11 slots in form kA | kB against 7 and 15), then the same two.
 // sched_barrier pins the fillers there: the scheduler does not model these hazards as latency
 // and leaves the later levels back to back, padded with s_nop.  (The empty asm ties each level
 // to its place among the barriers: the DPP intrinsics have no side effects, and instruction
 // selection otherwise emits a level behind the next gap's fillers.)  A gap left short is padded
 // by the compiler.  Same operations in the same order as the plain forms: identical bits.
-constexpr int kFillGaps = 8;
-constexpr int kFillSlots[kFillGaps] = {2, 2, 2, 2, 2, 2, 1, 2};
+constexpr int fill_gaps(int F) { return red::stages(F) + 2; }
+constexpr int fill_slots(int F, int G) { return G == fill_gaps(F) - 2 ? 1 : 2; }
+// the gap that holds the wait for the next step's emission row (band_chain, PW): form 0 ahead of
+// row_bcast:15, else ahead of row_bcast:31, which a step with eight
+// fillers still leaves empty where it fills the one ahead of row_bcast:15
+constexpr int emis_wait_gap(int F) {
+#ifdef HMM355_EMIS_WAIT_GAP
+  return HMM355_EMIS_WAIT_GAP;
+#else
+  return F == 0 ? 4 : red::stages(F) - 1;
+#endif
+}
 // The fillers of gap G when the caller has NU of them: whole gaps first, the gap behind
 // v_readlane, then gaps 0, 1, 2 ... (a gap filled by half still costs its s_nop: of the
 // allocations measured -- in proportion to the slots, from the back, from the front -- this one
 // ran fastest); what exceeds all slots goes behind v_readlane too.
-constexpr int fill_cnt(int G, int NU) {
+constexpr int fill_cnt(int G, int NU, int F = 0) {
+  const int NG = fill_gaps(F);
   int rem = NU, all = 0;
-  for (int i = 0; i < kFillGaps; ++i) all += kFillSlots[i];
-  for (int i = 0; i < kFillGaps; ++i) {
-    const int g = i == 0 ? kFillGaps - 1 : i - 1;
-    const int c = kFillSlots[g] < rem ? kFillSlots[g] : rem;
-    if (g == G) return c + (G == kFillGaps - 1 && NU > all ? NU - all : 0);
+  for (int i = 0; i < NG; ++i) all += fill_slots(F, i);
+  for (int i = 0; i < NG; ++i) {
+    const int g = i == 0 ? NG - 1 : i - 1;
+    const int c = fill_slots(F, g) < rem ? fill_slots(F, g) : rem;
+    if (g == G) return c + (G == NG - 1 && NU > all ? NU - all : 0);
     rem -= c;
   }
   return 0;
 }
 // fillers [fill_lo(G), fill_lo(G + 1)) go to gap G: in the caller's order
-constexpr int fill_lo(int G, int NU) {
+constexpr int fill_lo(int G, int NU, int F = 0) {
   int lo = 0;
-  for (int g = 0; g < G; ++g) lo += fill_cnt(g, NU);
+  for (int g = 0; g < G; ++g) lo += fill_cnt(g, NU, F);
   return lo;
 }
 __device__ __forceinline__ void fill_pin(float& x) { asm volatile("" : "+v"(x)); }
-template <bool MAX, typename F>
-__device__ __forceinline__ float wave_red_fill(float x, F&& fill) {
-  static_for<0, 6>([&](auto L) {
+template <bool MAX, int F = 0, typename FILL>
+__device__ __forceinline__ float wave_red_fill(float x, FILL&& fill) {
+  constexpr int NS = red::stages(F);
+  static_for<0, NS>([&](auto S) {
     __builtin_amdgcn_sched_barrier(0);
-    fill(L);
+    fill(S);
     __builtin_amdgcn_sched_barrier(0);
-    x = wave_red_level<MAX, decltype(L)::value>(x);
-    fill_pin(x);
+    x = wave_red_level<MAX, decltype(S)::value, F, true>(x);
+    if constexpr (!red::triple_at(F, red::level(F, decltype(S)::value))) fill_pin(x);
   });
   __builtin_amdgcn_sched_barrier(0);
-  fill(std::integral_constant<int, 6>{});
+  fill(std::integral_constant<int, NS>{});
   __builtin_amdgcn_sched_barrier(0);
   x = wave_lane63(x);
   __builtin_amdgcn_sched_barrier(0);
-  fill(std::integral_constant<int, 7>{});
+  fill(std::integral_constant<int, NS + 1>{});
   __builtin_amdgcn_sched_barrier(0);
   return x;
 }
+
+#if HMM355_RED_PROBE
+// diagnostic builds (tools/probe_wave_reduce.py): one wave per 64-lane vector of `in`;
+// out[v][F] the maximum and out[v][4 + F] the sum of vector v by form F = 0 .. 3
+static __global__ void red_probe_kernel(const float* in, float* out, int n) {
+  const int v = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  if (v >= n) return;
+  const float x = in[(size_t)v * kWave + (threadIdx.x & (kWave - 1))];
+  static_for<0, 4>([&](auto F) {
+    const float m = wave_max_bcast<decltype(F)::value>(x), s = wave_sum_bcast<decltype(F)::value>(x);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      out[(size_t)v * 8 + decltype(F)::value] = m;
+      out[(size_t)v * 8 + 4 + decltype(F)::value] = s;
+    }
+  });
+}
+#endif
 
 // The banded FB step sums NB products p_j * e_j (the input of the normaliser's reduction) that
 // are also needed one by one.  Left to fp contraction (hipcc's default is fast) the backend
@@ -1373,12 +1483,13 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   // ES: the slot of `en` the step takes its emission from and reads enext into (no_read: nothing
   // left to read in this block)
   // PW (EA = 2, the chains whose reduction is filled): the wait for the NEXT step's row, read a
-  // step ago, stands in gap kEmisWaitGap of this step's reduction, where it takes the place of a
+  // step ago, stands in gap emis_wait_gap of this step's reduction, where it takes the place of a
   // wait state the level behind it needs anyway; left to the compiler it stands ahead of the
   // row's first use, an issue slot of its own in every step
   auto step = [&](int q, int jj, bool no_read, auto UA, auto FP, auto RL, auto ES, auto PW, float* row, const float* enext,
                   float& blk, auto wlane) {
     constexpr bool FILLED = KIND != kFbAlpha;
+    constexpr int RF = red_form(KIND);  // the form of the step's reductions (wave_red_level)
     constexpr bool LW = TW == 0;                                     // LDS-window mode
     constexpr bool WFILL = !(KIND == kFbAlpha && !decltype(UA)::value);  // the window terms are fillers
     constexpr int NWIN = NB * WW;
@@ -1448,8 +1559,8 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
       }
     };
     auto fill = [&](auto G) {
-      static_for<fill_lo(decltype(G)::value, NU), fill_lo(decltype(G)::value + 1, NU)>(unit);
-      if constexpr (decltype(PW)::value && decltype(G)::value == kEmisWaitGap && !(kAbl & abl::kBandEmisReg))
+      static_for<fill_lo(decltype(G)::value, NU, RF), fill_lo(decltype(G)::value + 1, NU, RF)>(unit);
+      if constexpr (decltype(PW)::value && decltype(G)::value == emis_wait_gap(RF) && !(kAbl & abl::kBandEmisReg))
         pin_all(en[EA - 1 - decltype(ES)::value]);
     };
     // (diagnostic timing bits, wrong results: kBandNoReduce no reduction, kBandReducePrev the
@@ -1460,13 +1571,13 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t)));
       } else if constexpr (!FILLED) {
         static_for<0, NU>(unit);
-        return decltype(MAXOP)::value ? wave_max_bcast(t) : wave_sum_bcast(t);
+        return decltype(MAXOP)::value ? wave_max_bcast<RF>(t) : wave_sum_bcast<RF>(t);
       } else if constexpr (decltype(MAXOP)::value && (kAbl & abl::kBandReducePrev)) {
-        const float r = wave_red_fill<true>(gprev, fill);
+        const float r = wave_red_fill<true, RF>(gprev, fill);
         gprev = t;
         return r;
       } else {
-        return wave_red_fill<decltype(MAXOP)::value>(t, fill);
+        return wave_red_fill<decltype(MAXOP)::value, RF>(t, fill);
       }
     };
     if (KIND == kFbBeta) {  // the product input is y = v * e_{q-1} (hmm.py:113-115)
@@ -1493,7 +1604,7 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
 #pragma unroll
         for (int j = 0; j < NB; ++j) tw = fmaf(y[j], fl[j], tw);
         cs = reduce(std::false_type{}, t);
-        tw = wave_sum_bcast(tw);
+        tw = wave_sum_bcast<RF>(tw);
 #pragma unroll
         for (int j = 0; j < NB; ++j) acc[j] = tw;
       }
