@@ -28,7 +28,7 @@
 // segments) and the next product input goes to the other LDS buffer: one s_barrier per
 // step.  The per-step source / emission / scale loads are issued PD steps ahead into a
 // register ring, so the chain never waits on HBM.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 
@@ -159,12 +159,7 @@ HMM355_API int hmm355_fb_adjoint_f32(const float* E, const float* log_P, const f
   if ((size_t)B * T > (size_t)1 << 40 || B > (1 << 30)) return HMM355_E_SHAPE;
   AdjArgs a{E, log_P, src_w, scale_w, src_z, scale_z, W, P, B, T, N};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int NP = pad_states(N);
-  switch (NP) {
-    case 64: hipLaunchKernelGGL(fb_adjoint_kernel<64>, dim3(2 * B), dim3(AdjGeo<64>::NT), 0, st, a); break;
-    case 128: hipLaunchKernelGGL(fb_adjoint_kernel<128>, dim3(2 * B), dim3(AdjGeo<128>::NT), 0, st, a); break;
-    default: hipLaunchKernelGGL(fb_adjoint_kernel<256>, dim3(2 * B), dim3(AdjGeo<256>::NT), 0, st, a); break;
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(pad_states(N), [&](auto np) {
+    return launch(fb_adjoint_kernel<np()>, dim3(2 * B), dim3(AdjGeo<np()>::NT), 0, st, a);
+  });
 }

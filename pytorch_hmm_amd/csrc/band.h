@@ -26,7 +26,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 
@@ -234,11 +234,8 @@ static __global__ void __launch_bounds__(kPrepThreads) band_prep_kernel(const fl
 // after the measurement, so every recursion of that plan takes the dense chains (parity tests
 // compare the two paths on the same inputs; the plan's tables are left as measured).
 inline hipError_t launch_band_prep(const float* log_P, int N, BandDesc* d, hipStream_t st, bool force_dense = false) {
-  hipLaunchKernelGGL(band_prep_kernel, dim3(1), dim3(kPrepThreads), 0, st, log_P, N, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && force_dense)
-    e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7fffffff, 2, st);  // wc, wr
-  return e;
+  HMM355_TRY(launch(band_prep_kernel, dim3(1), dim3(kPrepThreads), 0, st, log_P, N, d));
+  return force_dense ? hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7fffffff, 2, st) : hipSuccess;  // wc, wr
 }
 
 }  // namespace hmm355

@@ -339,22 +339,7 @@ inline bool stream_capturing(hipStream_t st) {
 static __global__ void zero_words_kernel(unsigned* p, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
 }
-inline hipError_t zero_words(void* p, size_t bytes, hipStream_t st) {
-  const int n = (int)((bytes + 3) / 4);
-  const int blocks = n < 256 * 64 ? (n + 255) / 256 : 64;
-  hipLaunchKernelGGL(zero_words_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, static_cast<unsigned*>(p), n);
-  return hipGetLastError();
-}
-// the counts before a publishing launch: a fresh token for an eager call, else token 0 and
-// the reset kernel
-inline hipError_t prepare_counts(void* p, size_t bytes, hipStream_t st, unsigned* token) {
-  if (!stream_capturing(st)) {
-    *token = next_count_token();
-    return hipSuccess;
-  }
-  *token = 0u;
-  return zero_words(p, bytes, st);
-}
+// (its launcher zero_words and prepare_counts: launch.h)
 
 inline int pad_states(int N) { return N <= 64 ? 64 : (N <= 128 ? 128 : 256); }
 

@@ -45,7 +45,7 @@
 // positions of a class are grouped once per workgroup (the labels' "next label of the same value"
 // links, formed in LDS); one lane sums a class's chain in position order and the blank's even
 // positions are summed by a fixed shuffle tree, so two runs give the same bits.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -469,21 +469,13 @@ HMM355_API int hmm355_ctc_f32(const float* log_probs, const int* targets, const 
   if (flags & HMM355_CTC_VITERBI) a.jobs[nj++] = kJobViterbi;
   const int Sm = 2 * Lmax + 1;
   hipStream_t sm = static_cast<hipStream_t>(stream);
-  const dim3 grid(B, nj);
-  if (Sm <= 64)
-    hipLaunchKernelGGL((ctc_kernel<1, 64>), grid, dim3(64), 0, sm, a);
-  else if (Sm <= kCtcThreads)
-    hipLaunchKernelGGL((ctc_kernel<1, kCtcThreads>), grid, dim3(kCtcThreads), 0, sm, a);
-  else if (Sm <= kCtcThreads * kCtcPosLow)
-    hipLaunchKernelGGL((ctc_kernel<kCtcPosLow, kCtcThreads>), grid, dim3(kCtcThreads), 0, sm, a);
-  else if (Sm <= kCtcThreads * kCtcPos)
-    hipLaunchKernelGGL((ctc_kernel<kCtcPos, kCtcThreads>), grid, dim3(kCtcThreads), 0, sm, a);
-  else if (Sm <= kCtcThreads * kCtcPosMid)
-    hipLaunchKernelGGL((ctc_kernel<kCtcPosMid, kCtcThreads>), grid, dim3(kCtcThreads), 0, sm, a);
-  else
-    hipLaunchKernelGGL((ctc_kernel<kCtcPosWide, kCtcThreads>), grid, dim3(kCtcThreads), 0, sm, a);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  const dim3 grid(B, nj), block(kCtcThreads);
+  if (Sm <= 64) return launch(ctc_kernel<1, 64>, grid, dim3(64), 0, sm, a);
+  if (Sm <= kCtcThreads) return launch(ctc_kernel<1, kCtcThreads>, grid, block, 0, sm, a);
+  if (Sm <= kCtcThreads * kCtcPosLow) return launch(ctc_kernel<kCtcPosLow, kCtcThreads>, grid, block, 0, sm, a);
+  if (Sm <= kCtcThreads * kCtcPos) return launch(ctc_kernel<kCtcPos, kCtcThreads>, grid, block, 0, sm, a);
+  if (Sm <= kCtcThreads * kCtcPosMid) return launch(ctc_kernel<kCtcPosMid, kCtcThreads>, grid, block, 0, sm, a);
+  return launch(ctc_kernel<kCtcPosWide, kCtcThreads>, grid, block, 0, sm, a);
 }
 
 HMM355_API int hmm355_ctc_grad_f32(const float* alpha, const float* beta, const float* loglik, const int* targets,
@@ -495,7 +487,5 @@ HMM355_API int hmm355_ctc_grad_f32(const float* alpha, const float* beta, const 
   if (!alpha || !beta || !loglik || !targets || !input_lengths || !target_lengths || !grad) return HMM355_E_ARG;
   CtcGradArgs a{alpha, beta, loglik, targets, input_lengths, target_lengths, gamma, grad, T, B, C, Lmax, blank};
   const dim3 grid(B, (T + kCtcGradRows - 1) / kCtcGradRows);
-  hipLaunchKernelGGL(ctc_grad_kernel, grid, dim3(kCtcThreads), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  return launch(ctc_grad_kernel, grid, dim3(kCtcThreads), 0, static_cast<hipStream_t>(stream), a);
 }

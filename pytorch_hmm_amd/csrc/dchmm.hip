@@ -37,7 +37,7 @@
 // the last step the same workgroup walks it back: it stages windows of as many time steps as its
 // LDS holds (4-byte loads) and one lane per sequence follows its path inside the window.  One
 // launch per call.
-#include "common.h"
+#include "launch.h"
 
 #include <climits>
 #include <cmath>
@@ -340,10 +340,7 @@ size_t dc_ws_bytes(int B, int T, int S) { return align_up((size_t)B * T * align_
 
 template <int R, bool LTL, int SPLIT = 1>
 hipError_t dc_launch(const DcArgs& a, int threads, size_t lds, hipStream_t st) {
-  const hipError_t e = allow_lds(dchmm_kernel<R, LTL, SPLIT>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((dchmm_kernel<R, LTL, SPLIT>), dim3((a.B + a.G - 1) / a.G), dim3(threads), lds, st, a);
-  return hipGetLastError();
+  return launch(dchmm_kernel<R, LTL, SPLIT>, dim3((a.B + a.G - 1) / a.G), dim3(threads), lds, st, a);
 }
 
 }  // namespace
@@ -394,14 +391,10 @@ HMM355_API int hmm355_dchmm_viterbi_f32(const float* emis, const float* log_T, i
   a.logS = (float)std::log((double)S);
   a.lds_bytes = (int)lds;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (R == 4)
-    e = lt_lds ? dc_launch<4, true>(a, threads, lds, st) : dc_launch<4, false>(a, threads, lds, st);
-  else if (R == 2)
-    e = lt_lds ? dc_launch<2, true>(a, threads, lds, st) : dc_launch<2, false>(a, threads, lds, st);
-  else if (split)
-    e = lt_lds ? dc_launch<1, true, kDcSplit>(a, threads, lds, st) : dc_launch<1, false, kDcSplit>(a, threads, lds, st);
-  else
-    e = lt_lds ? dc_launch<1, true>(a, threads, lds, st) : dc_launch<1, false>(a, threads, lds, st);
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  return with_flag(lt_lds, [&](auto ltl) {
+    if (R == 4) return dc_launch<4, ltl()>(a, threads, lds, st);
+    if (R == 2) return dc_launch<2, ltl()>(a, threads, lds, st);
+    if (split) return dc_launch<1, ltl(), kDcSplit>(a, threads, lds, st);
+    return dc_launch<1, ltl()>(a, threads, lds, st);
+  });
 }

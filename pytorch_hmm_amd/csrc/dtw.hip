@@ -24,7 +24,7 @@
 // diagonal, (i-1,j), (i,j-1) (dtw.py:127-143); that direction is recorded while the three
 // predecessors are in hand, 2 bits per cell (one byte per row and column block), and one lane
 // walks it afterwards through windows of the table staged in LDS.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -493,11 +493,14 @@ __global__ void __launch_bounds__(kDtwThreads) softdtw_grad_kernel(GradArgs a) {
 // edge (B,4Q) fp32 | dirs (B,N,Q) bytes | rev_i | rev_j (B,N+M-1) int32, pieces 256-B aligned;
 // false on overflow
 struct DtwWs {
-  size_t edge, dirs, rev_i, rev_j, total;
+  float* edge;
+  unsigned char* dirs;
+  int *rev_i, *rev_j;
+  size_t total;
 };
 bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
 
-bool dtw_layout(int B, int N, int M, unsigned flags, DtwWs* w) {
+bool dtw_layout(int B, int N, int M, unsigned flags, char* base, DtwWs* w) {
   const size_t Q = ((size_t)M + 3) / 4, P = (size_t)N + M - 1;
   const size_t lim = (size_t)1 << 46;
   size_t cells, edge, dirs = 0, rev = 0;
@@ -506,13 +509,12 @@ bool dtw_layout(int B, int N, int M, unsigned flags, DtwWs* w) {
   if (flags & HMM355_DTW_PATH) {
     if (!mul_ok((size_t)B * N, Q, &dirs) || !mul_ok((size_t)B, P * 4, &rev) || dirs > lim || rev > lim) return false;
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  w->edge = take(edge);
-  w->dirs = take(dirs);
-  w->rev_i = take(rev);
-  w->rev_j = take(rev);
-  w->total = off;
+  Carver c{base};
+  w->edge = c.take<float>(edge / sizeof(float));
+  w->dirs = c.take<unsigned char>(dirs);
+  w->rev_i = c.take<int>(rev / sizeof(int));
+  w->rev_j = c.take<int>(rev / sizeof(int));
+  w->total = c.bytes();
   return true;
 }
 
@@ -533,17 +535,11 @@ int dtw_shape_check(int B, int N, int M) {
 
 using namespace hmm355;
 
-#define DTW_LAUNCHED()                               \
-  do {                                               \
-    const hipError_t e_ = hipGetLastError();         \
-    if (e_ != hipSuccess) return (int)e_;            \
-  } while (0)
-
 HMM355_API size_t hmm355_dtw_workspace_bytes(int B, int N, int M, unsigned flags) {
   if (dtw_shape_check(B, N, M) != HMM355_OK) return 0;
   if (flags & ~HMM355_DTW_PATH) return 0;
   DtwWs w;
-  if (!dtw_layout(B, N, M, flags, &w)) return 0;
+  if (!dtw_layout(B, N, M, flags, nullptr, &w)) return 0;
   return w.total;
 }
 
@@ -561,20 +557,19 @@ HMM355_API int hmm355_dtw_f32(const float* dist, const int* n_len, const int* m_
   if (want_path && (!path_i || !path_j || !path_len)) return HMM355_E_ARG;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return HMM355_E_ARG;
   DtwWs w;
-  if (!dtw_layout(B, N, M, flags, &w)) return HMM355_E_SHAPE;
+  if (!dtw_layout(B, N, M, flags, static_cast<char*>(workspace), &w)) return HMM355_E_SHAPE;
   if (workspace_bytes < w.total) return HMM355_E_WORKSPACE;
-  char* base = static_cast<char*>(workspace);
   DtwArgs a{};
   a.dist = dist;
   a.n_len = n_len;
   a.m_len = m_len;
   a.cost = cost_matrix;
   a.total = total;
-  a.edge = reinterpret_cast<float*>(base + w.edge);
+  a.edge = w.edge;
   if (want_path) {
-    a.dirs = reinterpret_cast<unsigned char*>(base + w.dirs);
-    a.rev_i = reinterpret_cast<int*>(base + w.rev_i);
-    a.rev_j = reinterpret_cast<int*>(base + w.rev_j);
+    a.dirs = w.dirs;
+    a.rev_i = w.rev_i;
+    a.rev_j = w.rev_j;
     a.path_i = path_i;
     a.path_j = path_j;
     a.path_len = path_len;
@@ -584,11 +579,8 @@ HMM355_API int hmm355_dtw_f32(const float* dist, const int* n_len, const int* m_
   hipStream_t sm = static_cast<hipStream_t>(stream);
   // asymmetric: min(c + d) = d + min(c) in fp32 (the add is monotone), the symmetric kernel
   if (pattern == HMM355_DTW_RABINER_JUANG)
-    hipLaunchKernelGGL(dtw_fwd_kernel<kModeRJ>, dim3(B), dim3(kDtwThreads), 0, sm, a);
-  else
-    hipLaunchKernelGGL(dtw_fwd_kernel<kModeSym>, dim3(B), dim3(kDtwThreads), 0, sm, a);
-  DTW_LAUNCHED();
-  return HMM355_OK;
+    return launch(dtw_fwd_kernel<kModeRJ>, dim3(B), dim3(kDtwThreads), 0, sm, a);
+  return launch(dtw_fwd_kernel<kModeSym>, dim3(B), dim3(kDtwThreads), 0, sm, a);
 }
 
 static bool gamma_ok(float g) { return g > 0.f && g < INFINITY; }
@@ -610,9 +602,7 @@ HMM355_API int hmm355_softdtw_f32(const float* dist, const int* n_len, const int
   a.M = M;
   a.gamma = gamma;
   a.inv_gamma = (float)(1.0 / (double)gamma);
-  hipLaunchKernelGGL(dtw_fwd_kernel<kModeSoft>, dim3(B), dim3(kDtwThreads), 0, static_cast<hipStream_t>(stream), a);
-  DTW_LAUNCHED();
-  return HMM355_OK;
+  return launch(dtw_fwd_kernel<kModeSoft>, dim3(B), dim3(kDtwThreads), 0, static_cast<hipStream_t>(stream), a);
 }
 
 HMM355_API int hmm355_softdtw_grad_f32(const float* dist, const float* R, const int* n_len, const int* m_len, int B,
@@ -624,7 +614,5 @@ HMM355_API int hmm355_softdtw_grad_f32(const float* dist, const float* R, const 
   if (!dist || !R || !E) return HMM355_E_ARG;
   // (dist is part of the signature; the weights are functions of R alone)
   GradArgs a{R, n_len, m_len, E, N, M, (float)(1.0 / (double)gamma)};
-  hipLaunchKernelGGL(softdtw_grad_kernel, dim3(B), dim3(kDtwThreads), 0, static_cast<hipStream_t>(stream), a);
-  DTW_LAUNCHED();
-  return HMM355_OK;
+  return launch(softdtw_grad_kernel, dim3(B), dim3(kDtwThreads), 0, static_cast<hipStream_t>(stream), a);
 }

@@ -53,7 +53,7 @@
 //     d loglik / d log_probs: the positions of a class are grouped once per workgroup ("next
 //     position of the same class" links in LDS) and one lane sums a class's chain of gammas in
 //     position order.  No atomics anywhere: two runs give the same bits.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -705,39 +705,39 @@ int df_shape_check(int B, int T, int C, int Lm, int Dm) {
   return HMM355_OK;
 }
 
+// (each layout ends with 256 bytes of slack)
 struct DfLayout {
-  size_t M, bp, total;
+  float* M;
+  unsigned char* bp;
+  size_t total;
 };
-DfLayout df_layout(int B, int T, int Lm, unsigned flags) {
+DfLayout df_layout(int B, int T, int Lm, unsigned flags, char* base) {
   DfLayout L{};
-  size_t o = 0;
-  L.M = o;
-  o += align_up((size_t)3 * B * T * 4, 256);
-  L.bp = o;
-  if (flags & HMM355_DURFORCED_VITERBI) o += align_up((size_t)B * T * Lm, 256);
-  L.total = o + 256;
+  Carver c{base};
+  L.M = c.take<float>((size_t)3 * B * T);
+  L.bp = c.take<unsigned char>((flags & HMM355_DURFORCED_VITERBI) ? (size_t)B * T * Lm : 0);
+  L.total = c.bytes() + 256;
   return L;
 }
 
 struct DfGradLayout {
-  size_t gamma, P, Cinf, part, total;
+  float* gamma;
+  double* P;
+  int* Cinf;
+  double* part;
+  size_t total;
   int chunks;
 };
-DfGradLayout df_grad_layout(int B, int T, int Lm, int Dm) {
+DfGradLayout df_grad_layout(int B, int T, int Lm, int Dm, char* base) {
   DfGradLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
+  Carver c{base};
   const size_t n = (size_t)B * T * Lm;
   L.chunks = df_chunks(Lm * Dm, T);
-  L.gamma = take(n * 4);
-  L.P = take(n * 8);
-  L.Cinf = take(n * 4);
-  L.part = take((size_t)B * L.chunks * Lm * Dm * 8);
-  L.total = o + 256;
+  L.gamma = c.take<float>(n);
+  L.P = c.take<double>(n);
+  L.Cinf = c.take<int>(n);
+  L.part = c.take<double>((size_t)B * L.chunks * Lm * Dm);
+  L.total = c.bytes() + 256;
   return L;
 }
 
@@ -749,8 +749,8 @@ using namespace hmm355;
 HMM355_API size_t hmm355_durforced_workspace_bytes(int B, int T, int Lmax, int Dmax, unsigned flags) {
   if (df_shape_check(B, T, 1, Lmax, Dmax) != HMM355_OK) return 0;
   if (flags & ~(kDfFlags | HMM355_DURFORCED_GRAD)) return 0;
-  const size_t run = df_layout(B, T, Lmax, flags).total;
-  const size_t grad = (flags & HMM355_DURFORCED_GRAD) ? df_grad_layout(B, T, Lmax, Dmax).total : 0;
+  const size_t run = df_layout(B, T, Lmax, flags, nullptr).total;
+  const size_t grad = (flags & HMM355_DURFORCED_GRAD) ? df_grad_layout(B, T, Lmax, Dmax, nullptr).total : 0;
   return run > grad ? run : grad;
 }
 
@@ -768,9 +768,8 @@ HMM355_API int hmm355_durforced_f32(const float* log_probs, const int* state_ids
   if (tables && (!begin || !F || !Bend || !Bbeg || !frame_shift || !loglik_shifted)) return HMM355_E_ARG;
   if ((flags & HMM355_DURFORCED_VITERBI) && (!path || !score || !durations)) return HMM355_E_ARG;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return HMM355_E_ARG;
-  const DfLayout L = df_layout(B, T, Lmax, flags);
+  const DfLayout L = df_layout(B, T, Lmax, flags, static_cast<char*>(workspace));
   if (workspace_bytes < L.total) return HMM355_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
   DfArgs a{};
   a.lp = log_probs;
   a.ids = state_ids;
@@ -789,8 +788,8 @@ HMM355_API int hmm355_durforced_f32(const float* log_probs, const int* state_ids
   a.path = path;
   a.score = score;
   a.durs = durations;
-  a.M = reinterpret_cast<float*>(ws + L.M);
-  a.bp = reinterpret_cast<unsigned char*>(ws + L.bp);
+  a.M = L.M;
+  a.bp = L.bp;
   a.B = B;
   a.T = T;
   a.C = C;
@@ -816,14 +815,9 @@ HMM355_API int hmm355_durforced_f32(const float* log_probs, const int* state_ids
                 "the padded ring and dur_lp fit");
   if (lds > kDfLdsBudget) return HMM355_E_STATES;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  auto launch = [&](auto kernel) -> hipError_t {
-    const hipError_t le = allow_lds(kernel, lds);
-    if (le != hipSuccess) return le;
-    hipLaunchKernelGGL(kernel, dim3(B, nj), dim3(a.NT), lds, st, a);
-    return hipGetLastError();
-  };
-  const hipError_t e = a.NT == 64 ? launch(durforced_chain_kernel<true>) : launch(durforced_chain_kernel<false>);
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  return with_flag(a.NT == 64, [&](auto one_wave) {
+    return launch(durforced_chain_kernel<one_wave()>, dim3(B, nj), dim3(a.NT), lds, st, a);
+  });
 }
 
 HMM355_API int hmm355_durforced_grad_f32(const float* begin, const float* F, const float* Bend, const float* Bbeg,
@@ -840,12 +834,11 @@ HMM355_API int hmm355_durforced_grad_f32(const float* begin, const float* F, con
   if (!gamma && !grad_log_probs && !grad_dur_lp) return HMM355_E_ARG;
   // the workspace holds gamma for the class sums when it is no output, and the counts' sums
   const bool need_ws = grad_dur_lp || (grad_log_probs && !gamma);
-  const DfGradLayout L = df_grad_layout(B, T, Lmax, Dmax);
+  const DfGradLayout L = df_grad_layout(B, T, Lmax, Dmax, static_cast<char*>(workspace));
   if (need_ws) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return HMM355_E_ARG;
     if (workspace_bytes < L.total) return HMM355_E_WORKSPACE;
   }
-  char* ws = static_cast<char*>(workspace);
   DfGradArgs a{};
   a.begin = begin;
   a.F = F;
@@ -858,13 +851,13 @@ HMM355_API int hmm355_durforced_grad_f32(const float* begin, const float* F, con
   a.in_len = input_lengths;
   a.st_len = state_lengths;
   a.dur = dur_lp;
-  a.gamma = gamma ? gamma : (grad_log_probs ? reinterpret_cast<float*>(ws + L.gamma) : nullptr);
+  a.gamma = gamma ? gamma : (grad_log_probs ? L.gamma : nullptr);
   a.grad = grad_log_probs;
   a.grad_dur = grad_dur_lp;
   if (grad_dur_lp) {
-    a.P = reinterpret_cast<double*>(ws + L.P);
-    a.Cinf = reinterpret_cast<int*>(ws + L.Cinf);
-    a.part = reinterpret_cast<double*>(ws + L.part);
+    a.P = L.P;
+    a.Cinf = L.Cinf;
+    a.part = L.part;
   }
   a.B = B;
   a.T = T;
@@ -878,20 +871,12 @@ HMM355_API int hmm355_durforced_grad_f32(const float* begin, const float* F, con
   a.n_red = grad_dur_lp ? B * a.cx : 0;
   a.tiles = (T + kDfClassRows - 1) / kDfClassRows;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
   // gamma workgroups, then one prefix-sum workgroup per sequence (a thread per position)
   static_assert(kDfMaxPos <= 64 * kDfGammaChunks, "the prefix sums of a sequence fit one workgroup");
-  hipLaunchKernelGGL(durforced_gamma_kernel, dim3(a.n_gamma + (grad_dur_lp ? B : 0)), dim3(64 * kDfGammaChunks), 0, st,
-                     a);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  if (grad_dur_lp) {
-    hipLaunchKernelGGL(durforced_count_kernel, dim3(B * a.chunks * a.cx), dim3(256), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  }
+  HMM355_TRY(launch(durforced_gamma_kernel, dim3(a.n_gamma + (grad_dur_lp ? B : 0)), dim3(64 * kDfGammaChunks), 0, st,
+                    a));
+  if (grad_dur_lp) HMM355_TRY(launch(durforced_count_kernel, dim3(B * a.chunks * a.cx), dim3(256), 0, st, a));
   const int n_cls = grad_log_probs ? B * a.tiles : 0;
-  if (a.n_red + n_cls > 0) {
-    hipLaunchKernelGGL(durforced_reduce_kernel, dim3(a.n_red + n_cls), dim3(256), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  }
-  return HMM355_OK;
+  if (a.n_red + n_cls == 0) return HMM355_OK;
+  return launch(durforced_reduce_kernel, dim3(a.n_red + n_cls), dim3(256), 0, st, a);
 }

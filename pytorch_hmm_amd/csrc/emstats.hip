@@ -28,7 +28,7 @@
 // keeps its own dims in phase B.  The span's sums go to a slab [span][2D + 1][PP] (fp32) and
 // es_reduce_kernel adds the spans in index order in fp64: no atomics, the same bits on every call.
 // Frames at t >= lengths[b] are selected out (x staged as 0, weight 0) and never read.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 
@@ -72,20 +72,14 @@ struct EsWs {
   float* slab;
 };
 static size_t es_ws_layout(const EsGeo& g, int S, int C, char* base, EsWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t tab = (size_t)g.PP * g.DP * sizeof(double);
-  const size_t ow = take(tab), om = take(tab), ou = take(tab);
-  const size_t oc = take((size_t)S * C * 2 * sizeof(double));
-  const size_t os = take(g.nspans * (size_t)g.K * g.PP * sizeof(float));
-  if (w && base) {
-    w->pw = reinterpret_cast<double*>(base + ow);
-    w->pmw = reinterpret_cast<double*>(base + om);
-    w->pmu = reinterpret_cast<double*>(base + ou);
-    w->cst = reinterpret_cast<double*>(base + oc);
-    w->slab = reinterpret_cast<float*>(base + os);
-  }
-  return off;
+  const size_t tab = (size_t)g.PP * g.DP;
+  Carver c{base};
+  w->pw = c.take<double>(tab);
+  w->pmw = c.take<double>(tab);
+  w->pmu = c.take<double>(tab);
+  w->cst = c.take<double>((size_t)S * C * 2);
+  w->slab = c.take<float>(g.nspans * (size_t)g.K * g.PP);
+  return c.bytes();
 }
 
 // the scorer's tables (gmm_prep_kernel: scales w = exp(-lv/2) and offsets -mu w, fp64, d-major
@@ -430,7 +424,8 @@ using namespace hmm355;
 
 HMM355_API size_t hmm355_gmm_stats_workspace_bytes(int B, int T, int D, int S, int C) {
   if (!es_shape_ok(B, T, D, S, C)) return 0;
-  return es_ws_layout(es_geo(B, T, D, S, C), S, C, nullptr, nullptr);
+  EsWs w;
+  return es_ws_layout(es_geo(B, T, D, S, C), S, C, nullptr, &w);
 }
 
 HMM355_API int hmm355_gmm_stats_f32(const float* x, const float* weight, const float* means, const float* log_vars,
@@ -450,18 +445,12 @@ HMM355_API int hmm355_gmm_stats_f32(const float* x, const float* weight, const f
   es_ws_layout(g, S, C, static_cast<char*>(workspace), &w);
   const int P = S * C;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(es_prep_kernel, dim3(g.PP), dim3(64), 0, st, means, log_vars, log_w, w.pw, w.pmw, w.pmu, w.cst, P,
-                     g.PP, D, g.DP);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  HMM355_TRY(launch(es_prep_kernel, dim3(g.PP), dim3(64), 0, st, means, log_vars, log_w, w.pw, w.pmw, w.pmu, w.cst, P,
+                    g.PP, D, g.DP));
   dim3 grid((unsigned)g.nspans, (unsigned)g.ngroups, (unsigned)g.nz);
-  hipLaunchKernelGGL(es_stats_kernel, grid, dim3(kEsThreads), 0, st, x, weight, lengths, w.pw, w.pmw, w.pmu, w.cst,
-                     w.slab, B * T, T, D, g.NDC, S, C, g.PP, g.NC, (int)g.ntiles, (int)g.tps, mix_lse);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  HMM355_TRY(launch(es_stats_kernel, grid, dim3(kEsThreads), 0, st, x, weight, lengths, w.pw, w.pmw, w.pmu, w.cst,
+                    w.slab, B * T, T, D, g.NDC, S, C, g.PP, g.NC, (int)g.ntiles, (int)g.tps, mix_lse));
   const size_t total = (size_t)g.K * g.PP;
-  hipLaunchKernelGGL(es_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.slab, (int)g.nspans,
-                     P, g.PP, D, occ, sx, sxx);
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return launch(es_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.slab, (int)g.nspans, P,
+                g.PP, D, occ, sx, sxx);
 }

@@ -63,30 +63,19 @@ struct FbWs {
 static size_t fb_ws_layout(int B, int T, int N, char* base, FbWs* w) {
   const size_t NP = pad_states(N);
   const size_t rows = (size_t)B * T;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t oU = take(2 * rows * NP * sizeof(float));
-  const size_t oL = take(2 * rows * sizeof(float));
-  const size_t oD = take(sizeof(BandDesc));
-  const size_t oI = take((size_t)B * NP * sizeof(float));
-  const size_t oS = take((size_t)B * sizeof(float));
-  const size_t oM = take(rows * sizeof(float));
-  const size_t oC = take(2 * rows * sizeof(float));
-  const size_t oP = take((size_t)2 * B * kPubStride * sizeof(int));
-  if (w && base) {
-    w->U = reinterpret_cast<float*>(base + oU);
-    w->V = w->U + rows * NP;
-    w->LA = reinterpret_cast<float*>(base + oL);
-    w->LB = w->LA + rows;
-    w->band = reinterpret_cast<BandDesc*>(base + oD);
-    w->binit = reinterpret_cast<float*>(base + oI);
-    w->bscale = reinterpret_cast<float*>(base + oS);
-    w->rmax = reinterpret_cast<float*>(base + oM);
-    w->CA = reinterpret_cast<float*>(base + oC);
-    w->CB = w->CA + rows;
-    w->pub = reinterpret_cast<int*>(base + oP);
-  }
-  return off;
+  Carver c{base};
+  w->U = c.take<float>(rows * NP);  // (NP is a multiple of 64: V follows U directly)
+  w->V = c.take<float>(rows * NP);
+  w->LA = c.take<float>(2 * rows);
+  w->LB = w->LA ? w->LA + rows : nullptr;
+  w->band = c.take<BandDesc>(1);
+  w->binit = c.take<float>((size_t)B * NP);
+  w->bscale = c.take<float>(B);
+  w->rmax = c.take<float>(rows);
+  w->CA = c.take<float>(2 * rows);
+  w->CB = w->CA ? w->CA + rows : nullptr;
+  w->pub = c.take<int>((size_t)2 * B * kPubStride);
+  return c.bytes();
 }
 
 // CUs of the current device, queried once per device (a relaxed atomic per slot)
@@ -108,7 +97,8 @@ using namespace hmm355;
 
 HMM355_API size_t hmm355_fb_workspace_bytes(int B, int T, int N) {
   if (B < 0 || T < 1 || N < 1 || N > 256) return 0;
-  return fb_ws_layout(B, T, N, nullptr, nullptr);
+  FbWs w;
+  return fb_ws_layout(B, T, N, nullptr, &w);
 }
 
 HMM355_API int hmm355_fb_workspace_layout(int B, int T, int N, size_t* offsets) {
@@ -127,9 +117,8 @@ HMM355_API size_t hmm355_plan_bytes(int N) { return (N >= 1 && N <= 256) ? sizeo
 HMM355_API int hmm355_plan_ex_f32(const float* log_P, int N, unsigned flags, void* plan, void* stream) {
   if (N < 1 || N > 256) return HMM355_E_STATES;
   if (!log_P || !plan || (flags & ~HMM355_PLAN_DENSE)) return HMM355_E_ARG;
-  const hipError_t e = launch_band_prep(log_P, N, static_cast<BandDesc*>(plan), static_cast<hipStream_t>(stream),
-                                        (flags & HMM355_PLAN_DENSE) != 0);
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return launch_band_prep(log_P, N, static_cast<BandDesc*>(plan), static_cast<hipStream_t>(stream),
+                          (flags & HMM355_PLAN_DENSE) != 0);
 }
 
 HMM355_API int hmm355_plan_f32(const float* log_P, int N, void* plan, void* stream) {
@@ -169,24 +158,14 @@ HMM355_API int hmm355_forward_backward_plan_f32(const float* obs, int obs_mode, 
   const float* binit = nullptr;
   const float* bscale = nullptr;
   if (log_beta_T) {
-    switch (NP) {
-      case 64: hipLaunchKernelGGL(beta_init_kernel<64>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-      case 128: hipLaunchKernelGGL(beta_init_kernel<128>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-      default: hipLaunchKernelGGL(beta_init_kernel<256>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-    }
-    const hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess) return (int)e0;
+    HMM355_TRY(launch_beta_init(NP, B, log_beta_T, N, w.binit, w.bscale, st));
     binit = w.binit;
     bscale = w.bscale;
   }
   const float* rmax = nullptr;
   if (obs_mode == HMM355_OBS_LOG) {
     const size_t rows = (size_t)B * T;
-    size_t blocks = (rows + 3) / 4;
-    blocks = blocks < 4096 ? blocks : 4096;
-    hipLaunchKernelGGL(row_max_kernel, dim3((unsigned)blocks), dim3(256), 0, st, obs, N, rows, w.rmax);
-    const hipError_t e1 = hipGetLastError();
-    if (e1 != hipSuccess) return (int)e1;
+    HMM355_TRY(launch(row_max_kernel, dim3(row_grid(rows, 4096)), dim3(256), 0, st, obs, N, rows, w.rmax));
     rmax = w.rmax;
   }
   RecArgs fa{obs, log_P, log_p0, w.U, w.LA, loglik, B, T, N, obs_mode, NP, band, nullptr, nullptr, nullptr, rmax, nullptr};
@@ -198,8 +177,7 @@ HMM355_API int hmm355_forward_backward_plan_f32(const float* obs, int obs_mode, 
       (size_t)T * NP * sizeof(float) < ((size_t)1 << 31)) {
     // both chains of a sequence in one workgroup, outputs formed inside it (fbpair.h)
     PairArgs pa{fa, fb, posterior, forward, backward, lik_ref, out_mask};
-    const hipError_t e = NP == 64 ? launch_fb_pair<64>(pa, B, st0) : launch_fb_pair<128>(pa, B, st0);
-    return e == hipSuccess ? HMM355_OK : (int)e;
+    return NP == 64 ? launch_fb_pair<64>(pa, B, st0) : launch_fb_pair<128>(pa, B, st0);
   }
   // the chains' flushes write forward / backward (exp(log u + LA), exp(log v + LB)) from their
   // LDS rows; the posterior pass then reads U / V and writes the posterior only
@@ -227,13 +205,7 @@ HMM355_API int hmm355_forward_backward_plan_f32(const float* obs, int obs_mode, 
   }
   PostArgs pa{w.U, w.V, w.LA, w.LB, posterior, forward, backward, lik_ref, B, T, N,
               out_mask & (HMM355_FB_POSTERIOR)};
-  hipError_t e;
-  switch (NP) {
-    case 64: e = launch_fb<64>(fa, fb, pa, plan == nullptr, st, nfollow); break;
-    case 128: e = launch_fb<128>(fa, fb, pa, plan == nullptr, st, nfollow); break;
-    default: e = launch_fb<256>(fa, fb, pa, plan == nullptr, st, nfollow); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(NP, [&](auto np) { return launch_fb<np()>(fa, fb, pa, plan == nullptr, st, nfollow); });
 }
 
 HMM355_API int hmm355_forward_backward_ex_f32(const float* obs, int obs_mode, const float* log_P,

@@ -27,7 +27,7 @@
 // j's, v_readlane hands it out), and the 64 drawn states of a chunk leave as one coalesced store.
 // In the global form the row load is issued before the step's look-ahead loads, so its wait does
 // not cover them (vmcnt counts in order).
-#include "common.h"
+#include "launch.h"
 
 #ifndef HMM355_FFBS_LDS_MAX_NP
 #define HMM355_FFBS_LDS_MAX_NP 128  // diagnostic builds (tools/time_ffbs.py): 0 reads A^T from global at every NP
@@ -242,10 +242,7 @@ size_t ffbs_ws(int N) {
 template <int NP, bool LDS>
 hipError_t ffbs_launch(const FfbsArgs& a, dim3 grid, hipStream_t st) {
   const size_t lds = LDS ? (size_t)NP * NP * sizeof(float) : 0;
-  const hipError_t e = allow_lds(ffbs_kernel<NP, LDS>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((ffbs_kernel<NP, LDS>), grid, dim3(kFfbsWaves * kWave), lds, st, a);
-  return hipGetLastError();
+  return launch(ffbs_kernel<NP, LDS>, grid, dim3(kFfbsWaves * kWave), lds, st, a);
 }
 
 }  // namespace
@@ -272,9 +269,7 @@ HMM355_API int hmm355_ffbs_f32(const float* fwd, int ld, const float* log_P, con
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int NP = pad_states(N);
   float* AT = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(ffbs_at_kernel, dim3(NP * NP / 256), dim3(256), 0, st, log_P, N, NP, AT);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  HMM355_TRY(launch(ffbs_at_kernel, dim3(NP * NP / 256), dim3(256), 0, st, log_P, N, NP, AT));
   // samples over blockIdx.y while the grid stays near 2048 workgroups (at least 8 per sequence), a
   // loop in the kernel beyond that
   int gy = (K + kFfbsWaves - 1) / kFfbsWaves;
@@ -283,10 +278,9 @@ HMM355_API int hmm355_ffbs_f32(const float* fwd, int ld, const float* log_P, con
   const dim3 grid((unsigned)B, (unsigned)gy);
   FfbsArgs a{fwd, AT, lengths, uniforms, states, ld, B, T, N, K};
   const bool lds = NP <= HMM355_FFBS_LDS_MAX_NP;
-  switch (NP) {
-    case 64: e = lds ? ffbs_launch<64, true>(a, grid, st) : ffbs_launch<64, false>(a, grid, st); break;
-    case 128: e = lds ? ffbs_launch<128, true>(a, grid, st) : ffbs_launch<128, false>(a, grid, st); break;
-    default: e = ffbs_launch<256, false>(a, grid, st); break;
+  switch (NP) {  // (no LDS form at NP = 256: not with_np)
+    case 64: return lds ? ffbs_launch<64, true>(a, grid, st) : ffbs_launch<64, false>(a, grid, st);
+    case 128: return lds ? ffbs_launch<128, true>(a, grid, st) : ffbs_launch<128, false>(a, grid, st);
+    default: return ffbs_launch<256, false>(a, grid, st);
   }
-  return e == hipSuccess ? HMM355_OK : (int)e;
 }

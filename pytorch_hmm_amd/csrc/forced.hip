@@ -56,7 +56,7 @@
 // order; a frame's normaliser is a fixed shuffle tree; the sums over t are taken by a thread per
 // position over its tile's frames in frame order (fp64), stored per tile in the workspace, and
 // forced_grad_combine_kernel adds the tiles in tile order.  Two runs give the same bits.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -599,21 +599,15 @@ size_t forced_grad_ws_bytes(int B, int T, int Smax) {
 }
 
 template <bool PLAIN>
-void forced_launch(const ForcedArgs& a, dim3 grid, hipStream_t sm) {
+hipError_t forced_launch(const ForcedArgs& a, dim3 grid, hipStream_t sm) {
   constexpr int NT = kForcedThreads;
   const int S = a.Smax;
-  if (S <= 64)
-    hipLaunchKernelGGL((forced_kernel<1, 64, PLAIN>), grid, dim3(64), 0, sm, a);
-  else if (S <= NT)
-    hipLaunchKernelGGL((forced_kernel<1, NT, PLAIN>), grid, dim3(NT), 0, sm, a);
-  else if (S <= NT * kForcedPosLow)
-    hipLaunchKernelGGL((forced_kernel<kForcedPosLow, NT, PLAIN>), grid, dim3(NT), 0, sm, a);
-  else if (S <= NT * kForcedPos)
-    hipLaunchKernelGGL((forced_kernel<kForcedPos, NT, PLAIN>), grid, dim3(NT), 0, sm, a);
-  else if (S <= NT * kForcedPosMid)
-    hipLaunchKernelGGL((forced_kernel<kForcedPosMid, NT, PLAIN>), grid, dim3(NT), 0, sm, a);
-  else
-    hipLaunchKernelGGL((forced_kernel<kForcedPosWide, NT, PLAIN>), grid, dim3(NT), 0, sm, a);
+  if (S <= 64) return launch(forced_kernel<1, 64, PLAIN>, grid, dim3(64), 0, sm, a);
+  if (S <= NT) return launch(forced_kernel<1, NT, PLAIN>, grid, dim3(NT), 0, sm, a);
+  if (S <= NT * kForcedPosLow) return launch(forced_kernel<kForcedPosLow, NT, PLAIN>, grid, dim3(NT), 0, sm, a);
+  if (S <= NT * kForcedPos) return launch(forced_kernel<kForcedPos, NT, PLAIN>, grid, dim3(NT), 0, sm, a);
+  if (S <= NT * kForcedPosMid) return launch(forced_kernel<kForcedPosMid, NT, PLAIN>, grid, dim3(NT), 0, sm, a);
+  return launch(forced_kernel<kForcedPosWide, NT, PLAIN>, grid, dim3(NT), 0, sm, a);
 }
 
 }  // namespace
@@ -669,12 +663,8 @@ HMM355_API int hmm355_forced_f32(const float* log_probs, const int* state_ids, c
   if (flags & HMM355_FORCED_VITERBI) a.jobs[nj++] = kJobViterbi;
   hipStream_t sm = static_cast<hipStream_t>(stream);
   const dim3 grid(B, nj);
-  if (!state_ids && !log_stay && !log_next && !log_skip)
-    forced_launch<true>(a, grid, sm);
-  else
-    forced_launch<false>(a, grid, sm);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  const bool plain = !state_ids && !log_stay && !log_next && !log_skip;
+  return with_flag(plain, [&](auto p) { return forced_launch<p()>(a, grid, sm); });
 }
 
 HMM355_API int hmm355_forced_grad_f32(const float* alpha, const float* beta, const float* loglik,
@@ -716,11 +706,8 @@ HMM355_API int hmm355_forced_grad_f32(const float* alpha, const float* beta, con
   a.part = trans ? static_cast<double*>(workspace) : nullptr;
   a.tiles = forced_grad_tiles(T);
   hipStream_t sm = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(forced_grad_kernel, dim3(B, a.tiles), dim3(kForcedThreads), 0, sm, a);
-  if (trans) {
-    const dim3 grid(B, (Smax + kForcedThreads - 1) / kForcedThreads);
-    hipLaunchKernelGGL(forced_grad_combine_kernel, grid, dim3(kForcedThreads), 0, sm, a);
-  }
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : HMM355_OK;
+  HMM355_TRY(launch(forced_grad_kernel, dim3(B, a.tiles), dim3(kForcedThreads), 0, sm, a));
+  if (!trans) return HMM355_OK;
+  const dim3 grid(B, (Smax + kForcedThreads - 1) / kForcedThreads);
+  return launch(forced_grad_combine_kernel, grid, dim3(kForcedThreads), 0, sm, a);
 }

@@ -27,7 +27,7 @@
 // fp64 parameters in VGPRs and updates the 64 frames' accumulators (two v_fma_f64 per (frame,
 // component, d), no LDS or vector-memory traffic in the inner loop).  The components' LSE
 // over c runs through a 16-frame LDS tile; rows leave as fp32.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 
@@ -407,9 +407,8 @@ static hipError_t launch_g4(const float* x, const double* pw, const double* pmw,
                             int L, hipStream_t st) {
   using G = G4<FG, NW, NF>;
   dim3 grid((unsigned)(((size_t)nframes + G::FT - 1) / G::FT), (unsigned)((P + G::CG - 1) / G::CG));
-  hipLaunchKernelGGL((gmm_score4_kernel<FG, NW, NF, REGP>), grid, dim3(G::NT), 0, st, x, pw, pmw, cst, out, nframes, D, NDC,
-                     S, C, P, PP, mix_lse, T, t0, L);
-  return hipGetLastError();
+  return launch(gmm_score4_kernel<FG, NW, NF, REGP>, grid, dim3(G::NT), 0, st, x, pw, pmw, cst, out, nframes, D, NDC,
+                S, C, P, PP, mix_lse, T, t0, L);
 }
 
 struct GmmWs {
@@ -438,20 +437,13 @@ static size_t gmm_ws_layout(int B, int T, int D, int S, int C, char* base, GmmWs
   const size_t NDC = (D + kGmmDc - 1) / kGmmDc, DP = NDC * kGmmDc;
   const size_t nframes = (size_t)B * T;
   const size_t ntiles = (nframes + kGmmFrames - 1) / kGmmFrames;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t ow = take(PP * DP * sizeof(double));
-  const size_t om = take(PP * DP * sizeof(double));
-  const size_t oc = take(P * 2 * sizeof(double));
+  Carver c{base};
+  w->pw = c.take<double>(PP * DP);
+  w->pmw = c.take<double>(PP * DP);
+  w->cst = c.take<double>(P * 2);
   // fp64 frame tiles: the first scorer only (v2 converts while staging)
-  const size_t ox = take(gmm_use_v1(C) ? ntiles * NDC * kGmmFrames * kGmmDc * sizeof(double) : 0);
-  if (w && base) {
-    w->pw = reinterpret_cast<double*>(base + ow);
-    w->pmw = reinterpret_cast<double*>(base + om);
-    w->cst = reinterpret_cast<double*>(base + oc);
-    w->xt = reinterpret_cast<double*>(base + ox);
-  }
-  return off;
+  w->xt = c.take<double>(gmm_use_v1(C) ? ntiles * NDC * kGmmFrames * kGmmDc : 0);
+  return c.bytes();
 }
 
 }  // namespace hmm355
@@ -460,7 +452,8 @@ using namespace hmm355;
 
 HMM355_API size_t hmm355_gmm_workspace_bytes(int B, int T, int D, int S, int C) {
   if (B < 0 || T < 0 || D < 1 || D > kGmmDMax || S < 1 || C < 1 || C > 256) return 0;
-  return gmm_ws_layout(B, T, D, S, C, nullptr, nullptr);
+  GmmWs w;
+  return gmm_ws_layout(B, T, D, S, C, nullptr, &w);
 }
 
 static int gmm_run(const float* x, const float* means, const float* log_vars, const float* log_w, int B, int T,
@@ -491,13 +484,13 @@ static int gmm_run(const float* x, const float* means, const float* log_vars, co
   const int nframes = B * L;  // (the v1 scorer below runs whole tensors only: L == T, t0 == 0)
   const size_t ntiles = ((size_t)nframes + kGmmFrames - 1) / kGmmFrames;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(gmm_prep_kernel, dim3(PP), dim3(64), 0, st, means, log_vars, log_w, w.pw, w.pmw, w.cst, P, PP,
-                     D, DP);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  HMM355_TRY(launch(gmm_prep_kernel, dim3(PP), dim3(64), 0, st, means, log_vars, log_w, w.pw, w.pmw, w.cst, P, PP, D,
+                    DP));
   const int cfg = gmm_cfg();  // diagnostic: 0 = the first scorer, 1.. = v2 shapes
   if (!gmm_use_v1(C)) {
     static_assert(G4<1, 4, 16>::CG == 256 && G4<2, 2, 16>::CG == 128 && G4<4, 2, 16>::CG == 64, "gmm_v2_group");
+    // (G4L / G4R stay macros: tests/test_gpu_gmm.py reads the default shapes, `: G4R(fg, nw, nf);`,
+    // from this text)
 #define G4L(fg, nw, nf) launch_g4<fg, nw, nf>(x, w.pw, w.pmw, w.cst, out, nframes, D, NDC, S, C, P, PP, mix_lse, T, t0, L, st)
     // shapes from tools/time_gmm.py (profiles/r4h_gmm2.log): config 3 (P = 512) 326 us with
     // 16 frames per lane; P = 64 (configs 2, 5) 57 / 34 us with 4 (the work is small: more waves)
@@ -506,31 +499,26 @@ static int gmm_run(const float* x, const float* means, const float* log_vars, co
     // call at configs 3 / 2 / 5; identical bits)
 #define G4R(fg, nw, nf) launch_g4<fg, nw, nf, true>(x, w.pw, w.pmw, w.cst, out, nframes, D, NDC, S, C, P, PP, mix_lse, T, t0, L, st)
     if (CG == 256) {
-      e = cfg == 1 ? G4L(1, 4, 16) : cfg == 2 ? G4L(1, 4, 8) : cfg == 3 ? G4L(1, 2, 16) : cfg == 4 ? G4L(1, 1, 16)
-                   : G4R(1, 4, 16);
+      return cfg == 1 ? G4L(1, 4, 16) : cfg == 2 ? G4L(1, 4, 8) : cfg == 3 ? G4L(1, 2, 16) : cfg == 4 ? G4L(1, 1, 16)
+                      : G4R(1, 4, 16);
     } else if (CG == 128) {
-      e = cfg == 1 ? G4L(2, 2, 8) : cfg == 2 ? G4L(2, 2, 16) : cfg == 3 ? G4L(2, 1, 8) : G4R(2, 2, 8);
+      return cfg == 1 ? G4L(2, 2, 8) : cfg == 2 ? G4L(2, 2, 16) : cfg == 3 ? G4L(2, 1, 8) : G4R(2, 2, 8);
     } else {
-      e = cfg == 1 ? G4L(4, 2, 4) : cfg == 2 ? G4L(4, 2, 8) : cfg == 3 ? G4L(4, 1, 4) : cfg == 4 ? G4L(4, 2, 16)
-                   : G4R(4, 2, 4);
+      return cfg == 1 ? G4L(4, 2, 4) : cfg == 2 ? G4L(4, 2, 8) : cfg == 3 ? G4L(4, 1, 4) : cfg == 4 ? G4L(4, 2, 16)
+                      : G4R(4, 2, 4);
     }
 #undef G4R
 #undef G4L
-    return e == hipSuccess ? HMM355_OK : (int)e;
   }
   const size_t total = ntiles * NDC * kGmmFrames * kGmmDc;
   size_t blocks = (total + 255) / 256;
   blocks = blocks < 8192 ? blocks : 8192;
-  hipLaunchKernelGGL(gmm_xt_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, w.xt, nframes, D, NDC, total);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  HMM355_TRY(launch(gmm_xt_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, w.xt, nframes, D, NDC, total));
   // a lane per (state, component): small S*C (GaussianHMMLayer / HSMMLayer, C = 1) gets
   // 64- or 128-thread workgroups instead of 256 threads of which most would idle
   const int nt = P <= 64 ? 64 : (P <= 128 ? 128 : (P <= 192 ? 192 : kGmmThreads));
   const int spb = nt / C;
   dim3 grid((unsigned)ntiles, (S + spb - 1) / spb);
-  hipLaunchKernelGGL(gmm_score_kernel, grid, dim3(nt), 0, st, w.xt, w.pw, w.pmw, w.cst, out, nframes, NDC,
-                     S, C, PP, mix_lse);
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return launch(gmm_score_kernel, grid, dim3(nt), 0, st, w.xt, w.pw, w.pmw, w.cst, out, nframes, NDC, S, C, PP,
+                mix_lse);
 }

@@ -49,7 +49,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 #include "tsum.h"
 
 namespace hmm355 {
@@ -965,30 +965,19 @@ template <int SUB, int NJ, int SMAX>
 static hipError_t launch_hsmm(const HsArgs& ha, const HsChunks& hc, unsigned flags, hipStream_t st) {
   using G = HsG<SUB, NJ, SMAX>;
   const size_t lds = sizeof(HsLds<SMAX, G::DW>);
-  hipError_t e = allow_lds(hsmm_fwd_kernel<SUB, NJ, SMAX>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((hsmm_fwd_kernel<SUB, NJ, SMAX>), dim3(ha.B), dim3(G::NT), lds, st, ha);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  HMM355_TRY(launch(hsmm_fwd_kernel<SUB, NJ, SMAX>, dim3(ha.B), dim3(G::NT), lds, st, ha));
   if constexpr (kAbl & abl::kHsmmForwardOnly) return hipSuccess;  // ablation: forward only (timing)
   const size_t blds = hsmm_walk_lds(ha.S, ha.Dm, G::R);
   if (hsmm_use_chunks(ha.T, flags)) {
     const size_t wlds = align16(blds) + kHsCap * sizeof(int4);
-    if ((e = allow_lds(hsmm_chunk_walk_kernel<G::R, SMAX>, wlds)) != hipSuccess) return e;
     HsChunks hs = hc;
     const long room = 163840 - (long)align16(blds) - 16;
     hs.stage = (int)std::min<long>(hc.C, std::max<long>(0, room / (long)(64 * sizeof(int4) + sizeof(int))));
     const size_t slds = align16(blds) + hs.stage * 64 * sizeof(int4) + hs.stage * sizeof(int);
-    if ((e = allow_lds(hsmm_stitch_kernel<G::R, SMAX>, slds)) != hipSuccess) return e;
-    hipLaunchKernelGGL((hsmm_chunk_walk_kernel<G::R, SMAX>), dim3(hc.C, ha.B), dim3(64), wlds, st, ha, hc);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((hsmm_stitch_kernel<G::R, SMAX>), dim3(ha.B), dim3(64), slds, st, ha, hs);
-    return hipGetLastError();
+    HMM355_TRY(launch(hsmm_chunk_walk_kernel<G::R, SMAX>, dim3(hc.C, ha.B), dim3(64), wlds, st, ha, hc));
+    return launch(hsmm_stitch_kernel<G::R, SMAX>, dim3(ha.B), dim3(64), slds, st, ha, hs);
   }
-  e = allow_lds(hsmm_backtrace_kernel<G::R, SMAX>, blds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((hsmm_backtrace_kernel<G::R, SMAX>), dim3(ha.B), dim3(64), blds, st, ha);
-  return hipGetLastError();
+  return launch(hsmm_backtrace_kernel<G::R, SMAX>, dim3(ha.B), dim3(64), blds, st, ha);
 }
 
 // One state (S = 1): the reference skips every s' == s candidate, so only the segment that
@@ -1055,9 +1044,8 @@ HMM355_API int hmm355_hsmm_viterbi_ex_f32(const float* lp, const float* dur_lp, 
   if ((size_t)B * T * S * Dmax > ((size_t)1 << 40)) return HMM355_E_SHAPE;
   if (workspace_bytes < hmm355_hsmm_workspace_bytes_ex(B, T, S, Dmax, flags)) return HMM355_E_WORKSPACE;
   if (hsmm_wide(S, Dmax, flags) && S > 1) {
-    const hipError_t e = launch_hsmm_wide(lp, dur_lp, log_T, B, T, S, Dmax, states, scores, workspace,
-                                          static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? HMM355_OK : (int)e;
+    return launch_hsmm_wide(lp, dur_lp, log_T, B, T, S, Dmax, states, scores, workspace,
+                            static_cast<hipStream_t>(stream));
   }
   const size_t n = (size_t)B * T * S;
   char* ws = static_cast<char*>(workspace);
@@ -1070,21 +1058,15 @@ HMM355_API int hmm355_hsmm_viterbi_ex_f32(const float* lp, const float* dur_lp, 
   HsArgs ha{lp, dur_lp, log_T, Mg, Dg, fin, scores, states, B, T, S, Dmax};
   HsChunks hc{rec, cnt, hsmm_chunks(T), hsmm_warm(), 0};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (S == 1) {
-    hipLaunchKernelGGL(hsmm_single_state_kernel, dim3(B), dim3(64), 0, st, ha);
-    e = hipGetLastError();
-    return e == hipSuccess ? HMM355_OK : (int)e;
-  }
+  if (S == 1) return launch(hsmm_single_state_kernel, dim3(B), dim3(64), 0, st, ha);
   // frames the walk never reaches (a segment without a predecessor path ends it) keep the
   // reference's torch.zeros initial value (hsmm.py:332)
-  if ((e = hipMemsetAsync(states, 0, (size_t)B * T * sizeof(int64_t), st)) != hipSuccess) return (int)e;
+  HMM355_TRY(hipMemsetAsync(states, 0, (size_t)B * T * sizeof(int64_t), st));
   switch (hsmm_cfg(S, Dmax)) {
-    case kHs4x16s64: e = launch_hsmm<4, 16, 64>(ha, hc, flags, st); break;
-    case kHs8x16: e = launch_hsmm<8, 16, 64>(ha, hc, flags, st); break;
-    default: e = launch_hsmm<4, 16, 128>(ha, hc, flags, st); break;
+    case kHs4x16s64: return launch_hsmm<4, 16, 64>(ha, hc, flags, st);
+    case kHs8x16: return launch_hsmm<8, 16, 64>(ha, hc, flags, st);
+    default: return launch_hsmm<4, 16, 128>(ha, hc, flags, st);
   }
-  return e == hipSuccess ? HMM355_OK : (int)e;
 }
 
 HMM355_API int hmm355_hsmm_viterbi_f32(const float* lp, const float* dur_lp, const float* log_T, int B, int T,

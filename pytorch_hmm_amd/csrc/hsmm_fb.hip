@@ -45,7 +45,7 @@
 //     chunk order.  Two runs give the same bits.
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -504,37 +504,37 @@ int hf_shape_check(int B, int T, int S, int Dm) {
   return HMM355_OK;
 }
 
+// (pieces an output flag does not ask for are not carved and stay null; 256 bytes of slack end it)
 struct HfLayout {
-  size_t ltF, ltB, M, lls, tab[4], P, Cinf, part, total;
+  float *ltF, *ltB, *M, *lls, *tab[4];
+  double* P;
+  int* Cinf;
+  double* part;
+  size_t total;
   int cd, ct;
 };
 
-HfLayout hf_layout(int B, int T, int S, int Dm, unsigned flags) {
+HfLayout hf_layout(int B, int T, int S, int Dm, unsigned flags, char* base) {
   HfLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
+  Carver c{base};
   const size_t n = (size_t)B * T * S;
-  L.ltF = take((size_t)S * S * 4);
-  L.ltB = take((size_t)S * S * 4);
-  L.M = take((size_t)B * T * 4);
-  L.lls = take((size_t)B * 4);
+  L.ltF = c.take<float>((size_t)S * S);
+  L.ltB = c.take<float>((size_t)S * S);
+  L.M = c.take<float>((size_t)B * T);
+  L.lls = c.take<float>(B);
   if (flags & kHfOutputs)
-    for (int k = 0; k < 4; ++k) L.tab[k] = take(n * 4);
+    for (int k = 0; k < 4; ++k) L.tab[k] = c.take<float>(n);
   L.cd = hf_chunks(S * Dm, T);
   L.ct = hf_chunks(S * S, T);
   if (flags & HMM355_HSMM_FB_DUR) {
-    L.P = take(n * 8);
-    L.Cinf = take(n * 4);
+    L.P = c.take<double>(n);
+    L.Cinf = c.take<int>(n);
   }
-  size_t part = 0;
-  if (flags & HMM355_HSMM_FB_DUR) part = (size_t)B * L.cd * S * Dm * 8;
-  if (flags & HMM355_HSMM_FB_TRANS) part = std::max(part, (size_t)B * L.ct * S * S * 8);
-  L.part = take(part);
-  L.total = o + 256;
+  size_t part = 0;  // (doubles)
+  if (flags & HMM355_HSMM_FB_DUR) part = (size_t)B * L.cd * S * Dm;
+  if (flags & HMM355_HSMM_FB_TRANS) part = std::max(part, (size_t)B * L.ct * S * S);
+  L.part = c.take<double>(part);
+  L.total = c.bytes() + 256;
   return L;
 }
 
@@ -545,7 +545,7 @@ using namespace hmm355;
 
 HMM355_API size_t hmm355_hsmm_fb_workspace_bytes(int B, int T, int S, int Dmax, unsigned flags) {
   if (hf_shape_check(B, T, S, Dmax) != HMM355_OK || (flags & ~kHfFlags)) return 0;
-  return hf_layout(B, T, S, Dmax, flags).total;
+  return hf_layout(B, T, S, Dmax, flags, nullptr).total;
 }
 
 HMM355_API int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const float* log_T, const float* log_init,
@@ -562,31 +562,26 @@ HMM355_API int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const fl
   if ((flags & HMM355_HSMM_FB_TRANS) && !trans_counts) return HMM355_E_ARG;
   if ((flags & HMM355_HSMM_FB_INIT) && !init_post) return HMM355_E_ARG;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return HMM355_E_ARG;
-  const HfLayout L = hf_layout(B, T, S, Dmax, flags);
+  const HfLayout L = hf_layout(B, T, S, Dmax, flags, static_cast<char*>(workspace));
   if (workspace_bytes < L.total) return HMM355_E_WORKSPACE;
 
-  char* ws = static_cast<char*>(workspace);
   const bool tables = flags & kHfOutputs;
   HfArgs a{};
   a.lp = lp;
   a.dur = dur_lp;
   a.logT = log_T;
   a.log_init = log_init;
-  a.ltF = reinterpret_cast<float*>(ws + L.ltF);
-  a.ltB = reinterpret_cast<float*>(ws + L.ltB);
-  a.M = reinterpret_cast<float*>(ws + L.M);
-  a.lls = reinterpret_cast<float*>(ws + L.lls);
+  a.ltF = L.ltF;
+  a.ltB = L.ltB;
+  a.M = L.M;
+  a.lls = L.lls;
   a.loglik = loglik;
-  if (tables) {
-    a.begin = reinterpret_cast<float*>(ws + L.tab[0]);
-    a.F = reinterpret_cast<float*>(ws + L.tab[1]);
-    a.Bend = reinterpret_cast<float*>(ws + L.tab[2]);
-    a.Bbeg = reinterpret_cast<float*>(ws + L.tab[3]);
-  }
-  if (flags & HMM355_HSMM_FB_DUR) {
-    a.P = reinterpret_cast<double*>(ws + L.P);
-    a.Cinf = reinterpret_cast<int*>(ws + L.Cinf);
-  }
+  a.begin = L.tab[0];
+  a.F = L.tab[1];
+  a.Bend = L.tab[2];
+  a.Bbeg = L.tab[3];
+  a.P = L.P;
+  a.Cinf = L.Cinf;
   a.B = B;
   a.T = T;
   a.S = S;
@@ -607,10 +602,8 @@ HMM355_API int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const fl
   if (flags & HMM355_HSMM_FB_DUR) a.jobs[nj++] = kJobPrefix;
 
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
   const int row_blocks = (int)(((size_t)B * T + 3) / 4);
-  hipLaunchKernelGGL(hsmm_fb_prep_kernel, dim3(row_blocks + (S * S + 255) / 256), dim3(256), 0, st, a, row_blocks);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  HMM355_TRY(launch(hsmm_fb_prep_kernel, dim3(row_blocks + (S * S + 255) / 256), dim3(256), 0, st, a, row_blocks));
 
   size_t lds = ((size_t)S * Dmax + 2 * (size_t)S) * 4;
   const size_t lt_bytes = (size_t)S * a.lt_stride * 4, du_bytes = (size_t)S * Dmax * 4;
@@ -620,19 +613,13 @@ HMM355_API int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const fl
   const bool du_lds = lds + du_bytes <= kHfLdsBudget;
   if (du_lds) lds += du_bytes;
   static_assert(2 * (size_t)kHfMaxCells * 4 + 2 * (size_t)kHfMaxStates * 4 <= kHfLdsBudget, "ring + dur_lp fit");
-  auto launch = [&](auto kernel) -> hipError_t {
-    const hipError_t le = allow_lds(kernel, lds);
-    if (le != hipSuccess) return le;
-    hipLaunchKernelGGL(kernel, dim3(B, nj), dim3(a.NT), lds, st, a);
-    return hipGetLastError();
-  };
+  const dim3 grid(B, nj), block(a.NT);
   if (lt_lds && du_lds)
-    e = launch(hsmm_fb_chain_kernel<true, true>);
+    HMM355_TRY(launch(hsmm_fb_chain_kernel<true, true>, grid, block, lds, st, a));
   else if (lt_lds)
-    e = launch(hsmm_fb_chain_kernel<true, false>);
+    HMM355_TRY(launch(hsmm_fb_chain_kernel<true, false>, grid, block, lds, st, a));
   else
-    e = launch(hsmm_fb_chain_kernel<false, true>);
-  if (e != hipSuccess) return (int)e;
+    HMM355_TRY(launch(hsmm_fb_chain_kernel<false, true>, grid, block, lds, st, a));
   if (!tables) return HMM355_OK;
 
   HfCountArgs c{};
@@ -648,33 +635,28 @@ HMM355_API int hmm355_hsmm_fb_f32(const float* lp, const float* dur_lp, const fl
   c.Cinf = a.Cinf;
   c.gamma = (flags & HMM355_HSMM_FB_GAMMA) ? gamma : nullptr;
   c.init_post = (flags & HMM355_HSMM_FB_INIT) ? init_post : nullptr;
-  c.part = reinterpret_cast<double*>(ws + L.part);
+  c.part = L.part;
   c.B = B;
   c.T = T;
   c.S = S;
   c.Dm = Dmax;
   if (c.gamma || c.init_post) {
     const int gx = c.gamma ? (S + 63) / 64 : 1;
-    hipLaunchKernelGGL(hsmm_fb_gamma_kernel, dim3(gx, B), dim3(64 * kHfGammaChunks), 0, st, c);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    HMM355_TRY(launch(hsmm_fb_gamma_kernel, dim3(gx, B), dim3(64 * kHfGammaChunks), 0, st, c));
   }
   if (flags & HMM355_HSMM_FB_DUR) {
     const int cells = S * Dmax;
     c.chunks = L.cd;
-    hipLaunchKernelGGL(hsmm_fb_dur_kernel, dim3((cells + 255) / 256, L.cd, B), dim3(256), 0, st, c);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(hsmm_fb_reduce_kernel, dim3((cells + 255) / 256, B), dim3(256), 0, st, c.part, dur_counts, cells,
-                       L.cd, S);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    HMM355_TRY(launch(hsmm_fb_dur_kernel, dim3((cells + 255) / 256, L.cd, B), dim3(256), 0, st, c));
+    HMM355_TRY(launch(hsmm_fb_reduce_kernel, dim3((cells + 255) / 256, B), dim3(256), 0, st, c.part, dur_counts,
+                      cells, L.cd, S));
   }
   if (flags & HMM355_HSMM_FB_TRANS) {
     const int cells = S * S;
     c.chunks = L.ct;
-    hipLaunchKernelGGL(hsmm_fb_trans_kernel, dim3((cells + 255) / 256, L.ct, B), dim3(256), 0, st, c);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(hsmm_fb_reduce_kernel, dim3((cells + 255) / 256, B), dim3(256), 0, st, c.part, trans_counts,
-                       cells, L.ct, 0);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    HMM355_TRY(launch(hsmm_fb_trans_kernel, dim3((cells + 255) / 256, L.ct, B), dim3(256), 0, st, c));
+    HMM355_TRY(launch(hsmm_fb_reduce_kernel, dim3((cells + 255) / 256, B), dim3(256), 0, st, c.part, trans_counts,
+                      cells, L.ct, 0));
   }
   return HMM355_OK;
 }

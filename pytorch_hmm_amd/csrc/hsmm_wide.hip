@@ -22,7 +22,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "launch.h"
 #include "tsum.h"
 
 namespace hmm355 {
@@ -253,17 +253,11 @@ hipError_t launch_hsmm_wide(const float* lp, const float* dur, const float* logT
   HwArgs a{lp, dur, logT, reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + align_up(n * 4, 256)),
            scores, states, B, T, S, Dm, tlds};
   // frames the walk never reaches keep the reference's torch.zeros value (hsmm.py:332)
-  hipError_t e = hipMemsetAsync(states, 0, (size_t)B * T * sizeof(int64_t), st);
-  if (e != hipSuccess) return e;
+  HMM355_TRY(hipMemsetAsync(states, 0, (size_t)B * T * sizeof(int64_t), st));
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(hsmm_wide_osum_kernel, dim3(blocks), dim3(256), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  HMM355_TRY(launch(hsmm_wide_osum_kernel, dim3(blocks), dim3(256), 0, st, a));
   const size_t lds = part + (tlds ? tab : 0);
-  e = allow_lds(hsmm_wide_kernel, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hsmm_wide_kernel, dim3(B), dim3(kHwNT), lds, st, a);
-  return hipGetLastError();
+  return launch(hsmm_wide_kernel, dim3(B), dim3(kHwNT), lds, st, a);
 }
 
 }  // namespace hmm355

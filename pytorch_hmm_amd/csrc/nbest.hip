@@ -39,7 +39,7 @@
 //
 // Padded states: init = -inf and log_P = -inf, so they never enter a rank.  Frames t >= len_b are
 // never read.
-#include "common.h"
+#include "launch.h"
 #include "logcr.h"
 
 namespace hmm355 {
@@ -366,10 +366,7 @@ int nb_check_shape(int B, int T, int N, int K, int obs_mode) {
 template <int NP, int KB>
 hipError_t nb_launch(const NbArgs& a, hipStream_t st) {
   using G = NbGeo<NP, KB>;
-  const hipError_t e = allow_lds(nbest_kernel<NP, KB>, G::LDS);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((nbest_kernel<NP, KB>), dim3(a.B), dim3(G::NT), G::LDS, st, a);
-  return hipGetLastError();
+  return launch(nbest_kernel<NP, KB>, dim3(a.B), dim3(G::NT), G::LDS, st, a);
 }
 
 template <int NP>
@@ -402,11 +399,5 @@ HMM355_API int hmm355_viterbi_nbest_f32(const float* obs, int obs_mode, const fl
   NbArgs a{obs, log_P, init, lengths, paths, scores, count, static_cast<uint16_t*>(workspace),
            B, T, N, K, obs_mode == HMM355_OBS_PROB};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  switch (pad_states(N)) {
-    case 64: e = nb_launch_k<64>(a, st); break;
-    case 128: e = nb_launch_k<128>(a, st); break;
-    default: e = nb_launch_k<256>(a, st); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(pad_states(N), [&](auto np) { return nb_launch_k<np()>(a, st); });
 }

@@ -345,5 +345,14 @@ __global__ void __launch_bounds__(64) beta_init_kernel(const float* __restrict__
   for (int k = 0; k < K; ++k) binit[(size_t)b * NP + l + 64 * k] = (l + 64 * k < N) ? __expf(v[k] - m) : 0.f;
   if (l == 0) bscale[b] = m;
 }
+// (a template only so that a translation unit that includes this header without calling it
+// instantiates no beta_init_kernel)
+template <typename Stream>
+inline hipError_t launch_beta_init(int NP, int B, const float* log_beta_T, int N, float* binit, float* bscale,
+                                   Stream st) {
+  return with_np(NP, [&](auto np) {
+    return launch(beta_init_kernel<np()>, dim3(B), dim3(64), 0, st, log_beta_T, N, binit, bscale);
+  });
+}
 
 }  // namespace hmm355

@@ -41,7 +41,7 @@
 // frames: log_delta = -inf, states = -1.
 //
 // The input in padded frames is never read.
-#include "common.h"
+#include "launch.h"
 #include "logcr.h"
 
 namespace hmm355 {
@@ -574,6 +574,12 @@ size_t rag_vit_ws(int B, int T, int N) { return align_up((size_t)B * T * pad_sta
 
 using namespace hmm355;
 
+// the float pieces of hmm355_fb_workspace_layout that the ragged op uses (offsets 0-3 and 6-9; the
+// BandDesc and the terminal vector, 4 and 5, are the dense op's)
+struct RagFbWs {
+  float *U, *V, *LA, *LB, *bscale, *rmax, *CA, *CB;
+};
+
 HMM355_API size_t hmm355_viterbi_ragged_workspace_bytes(int B, int T, int N, int obs_mode) {
   if (B < 0 || T < 1 || N < 1 || N > 256) return 0;
   if (obs_mode != HMM355_OBS_PROB && obs_mode != HMM355_OBS_LOG) return 0;
@@ -596,17 +602,12 @@ HMM355_API int hmm355_viterbi_ragged_f32(const float* obs, int obs_mode, const f
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int NP = pad_states(N);
   const bool prob = obs_mode == HMM355_OBS_PROB;
-#define HMM355_RAG_VIT(NPV)                                                                                      \
-  if (prob) hipLaunchKernelGGL((rag_vit_kernel<NPV, HMM355_OBS_PROB>), dim3(B), dim3(RagGeo<NPV>::NT), 0, st, a); \
-  else hipLaunchKernelGGL((rag_vit_kernel<NPV, HMM355_OBS_LOG>), dim3(B), dim3(RagGeo<NPV>::NT), 0, st, a)
-  switch (NP) {
-    case 64: HMM355_RAG_VIT(64); break;
-    case 128: HMM355_RAG_VIT(128); break;
-    default: HMM355_RAG_VIT(256); break;
-  }
-#undef HMM355_RAG_VIT
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(NP, [&](auto np) {
+    return with_flag(prob, [&](auto p) {
+      constexpr int OBS = p() ? HMM355_OBS_PROB : HMM355_OBS_LOG;
+      return launch(rag_vit_kernel<np(), OBS>, dim3(B), dim3(RagGeo<np()>::NT), 0, st, a);
+    });
+  });
 }
 
 HMM355_API int hmm355_forward_backward_ragged_f32(const float* obs, int obs_mode, const float* log_P,
@@ -626,49 +627,32 @@ HMM355_API int hmm355_forward_backward_ragged_f32(const float* obs, int obs_mode
   if (obs_mode != HMM355_OBS_PROB && obs_mode != HMM355_OBS_LOG) return HMM355_E_ARG;
   if ((size_t)B * T > (size_t)1 << 40 || B > (1 << 30)) return HMM355_E_SHAPE;
   if (workspace_bytes < hmm355_fb_workspace_bytes(B, T, N)) return HMM355_E_WORKSPACE;
-  // the pieces of hmm355_fb_workspace_layout: U, V, LA, LB, BandDesc, beta init, its scale, M, CA, CB
+  // the pieces of hmm355_fb_workspace_layout, by name
   size_t off[10];
   const int rc = hmm355_fb_workspace_layout(B, T, N, off);
   if (rc != HMM355_OK) return rc;
   char* base = static_cast<char*>(workspace);
   auto piece = [&](int i) { return reinterpret_cast<float*>(base + off[i]); };
+  const RagFbWs w{piece(0), piece(1), piece(2), piece(3), piece(6), piece(7), piece(8), piece(9)};
   const int NP = pad_states(N);
   const size_t rows = (size_t)B * T;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool prob = obs_mode == HMM355_OBS_PROB;
-  if (!prob) {
-    size_t blocks = (rows + 3) / 4;
-    blocks = blocks < 4096 ? blocks : 4096;
-    hipLaunchKernelGGL(rag_row_max_kernel, dim3((unsigned)blocks), dim3(256), 0, st, obs, lengths, T, N, rows, piece(7));
-    const hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess) return (int)e0;
-  }
-  RagFbArgs fa{obs, log_P, log_p0, log_beta_T, lengths, piece(7), piece(0), piece(1), piece(8), piece(9), piece(6), B, T, N};
-#define HMM355_RAG_FB(NPV)                                                                                           \
-  if (prob) hipLaunchKernelGGL((rag_fb_kernel<NPV, HMM355_OBS_PROB>), dim3(2 * B), dim3(RagGeo<NPV>::NT), 0, st, fa); \
-  else hipLaunchKernelGGL((rag_fb_kernel<NPV, HMM355_OBS_LOG>), dim3(2 * B), dim3(RagGeo<NPV>::NT), 0, st, fa)
-  switch (NP) {
-    case 64: HMM355_RAG_FB(64); break;
-    case 128: HMM355_RAG_FB(128); break;
-    default: HMM355_RAG_FB(256); break;
-  }
-#undef HMM355_RAG_FB
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  RagPostArgs pa{piece(0), piece(1), piece(2), piece(3), piece(8), piece(9), piece(7), piece(6), lengths,
+  if (!prob)
+    HMM355_TRY(launch(rag_row_max_kernel, dim3(row_grid(rows, 4096)), dim3(256), 0, st, obs, lengths, T, N, rows,
+                      w.rmax));
+  RagFbArgs fa{obs, log_P, log_p0, log_beta_T, lengths, w.rmax, w.U, w.V, w.CA, w.CB, w.bscale, B, T, N};
+  HMM355_TRY(with_np(NP, [&](auto np) {
+    return with_flag(prob, [&](auto p) {
+      constexpr int OBS = p() ? HMM355_OBS_PROB : HMM355_OBS_LOG;
+      return launch(rag_fb_kernel<np(), OBS>, dim3(2 * B), dim3(RagGeo<np()>::NT), 0, st, fa);
+    });
+  }));
+  RagPostArgs pa{w.U, w.V, w.LA, w.LB, w.CA, w.CB, w.rmax, w.bscale, lengths,
                  posterior, forward, backward, loglik, lik_ref, B, T, N, NP, obs_mode, out_mask};
-  hipLaunchKernelGGL(rag_scan_kernel, dim3(B), dim3(256), 0, st, pa);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  if (out_mask || lik_ref) {
-    size_t blocks = (rows + 3) / 4;
-    blocks = blocks < 8192 ? blocks : 8192;
-    switch (NP) {
-      case 64: hipLaunchKernelGGL(rag_post_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, pa); break;
-      case 128: hipLaunchKernelGGL(rag_post_kernel<128>, dim3((unsigned)blocks), dim3(256), 0, st, pa); break;
-      default: hipLaunchKernelGGL(rag_post_kernel<256>, dim3((unsigned)blocks), dim3(256), 0, st, pa); break;
-    }
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  HMM355_TRY(launch(rag_scan_kernel, dim3(B), dim3(256), 0, st, pa));
+  if (!out_mask && !lik_ref) return HMM355_OK;
+  return with_np(NP, [&](auto np) {
+    return launch(rag_post_kernel<np()>, dim3(row_grid(rows, 8192)), dim3(256), 0, st, pa);
+  });
 }

@@ -40,7 +40,7 @@
 // smk_backtrace_kernel  one wave per sequence walks the segments back (semi_markov.py:548-568).
 #include <stdlib.h>
 
-#include "common.h"
+#include "launch.h"
 
 #pragma clang fp contract(off)
 
@@ -631,10 +631,8 @@ HMM355_API int hmm355_semimarkov_quad_f32(const float* x, const float* means_t, 
   const long long F = (long long)B * T;
   if (F == 0) return HMM355_OK;
   if (!x || !means_t || !vars_t || !quad) return HMM355_E_ARG;
-  hipLaunchKernelGGL(smk_quad_kernel, dim3((unsigned)((F + 3) / 4), (unsigned)((S + 63) / 64)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, means_t, vars_t, (int)F, Df, S, quad);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return launch(smk_quad_kernel, dim3((unsigned)((F + 3) / 4), (unsigned)((S + 63) / 64)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), x, means_t, vars_t, (int)F, Df, S, quad);
 }
 
 static int smk_run(bool viterbi, const float* quad, const float* seg_const, const float* log_init,
@@ -655,19 +653,11 @@ static int smk_run(bool viterbi, const float* quad, const float* seg_const, cons
               reinterpret_cast<float*>(ws + align_up(n * 4, 256)), scores, alpha, seg_states, seg_durs, seg_count,
               B, T, S, Dmax};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(smk_wide_osum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    HMM355_TRY(launch(smk_wide_osum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wa));
     const size_t lds = (viterbi ? 1 : 2) * (kSwNT / 64) * (size_t)S * sizeof(float);
-    if (viterbi) {
-      if ((e = allow_lds(smk_wide_kernel<true>, lds)) != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(smk_wide_kernel<true>, dim3(B), dim3(kSwNT), lds, st, wa);
-    } else {
-      if ((e = allow_lds(smk_wide_kernel<false>, lds)) != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(smk_wide_kernel<false>, dim3(B), dim3(kSwNT), lds, st, wa);
-    }
-    e = hipGetLastError();
-    return e == hipSuccess ? HMM355_OK : (int)e;
+    return with_flag(viterbi, [&](auto vit) {
+      return launch(smk_wide_kernel<vit()>, dim3(B), dim3(kSwNT), lds, st, wa);
+    });
   }
   float* Mg = reinterpret_cast<float*>(ws);
   uint8_t* argS = reinterpret_cast<uint8_t*>(ws + 2 * align_up(n * 4, 256));
@@ -675,21 +665,10 @@ static int smk_run(bool viterbi, const float* quad, const float* seg_const, cons
   SmArgs sa{quad, seg_const, log_init, log_T, dur_lp, Mg, argS, fin, scores, alpha,
             seg_states, seg_durs, seg_count, B, T, S, Dmax};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (viterbi) {
-    e = allow_lds(smk_fwd_kernel<true>, sizeof(SmLds));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(smk_fwd_kernel<true>, dim3(B), dim3(kSmThreads), sizeof(SmLds), st, sa);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(smk_backtrace_kernel, dim3(B), dim3(64), 0, st, sa);
-  } else {
-    e = allow_lds(smk_fwd_kernel<false>, sizeof(SmLds));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(smk_fwd_kernel<false>, dim3(B), dim3(kSmThreads), sizeof(SmLds), st, sa);
-  }
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  HMM355_TRY(with_flag(viterbi, [&](auto vit) {
+    return launch(smk_fwd_kernel<vit()>, dim3(B), dim3(kSmThreads), sizeof(SmLds), st, sa);
+  }));
+  return viterbi ? launch(smk_backtrace_kernel, dim3(B), dim3(64), 0, st, sa) : hipSuccess;
 }
 
 HMM355_API int hmm355_semimarkov_viterbi_ex_f32(const float* quad, const float* seg_const, const float* log_init,

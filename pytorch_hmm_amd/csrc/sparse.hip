@@ -44,7 +44,7 @@
 //
 // Frames t >= len_b are never read.  An arc's other end is clamped into [0, N) and a row pointer
 // into [0, E] as read, so a wrong device array cannot index out of bounds.
-#include "common.h"
+#include "launch.h"
 
 namespace hmm355 {
 namespace {
@@ -645,17 +645,21 @@ size_t sp_vit_lds(int N) {
 size_t sp_vit_ws(int B, int T, int N) { return align_up((size_t)B * T * sp_bp_stride(N) * 2, 256); }
 
 // the forward-backward workspace: U, V (B,T,N); CA, rmax, Q1, Q2 (B,T); A by destination, A by source (E)
-constexpr int kSpFbPieces = 8;
-size_t sp_fb_layout(int B, int T, int N, int E, size_t* off) {
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += align_up(bytes, 256); return o; };
+struct SpFbWs {
+  float *U, *V, *CA, *rmax, *Q1, *Q2, *Ain, *Aout;
+};
+size_t sp_fb_layout(int B, int T, int N, int E, char* base, SpFbWs* w) {
   const size_t rows = (size_t)B * T;
-  off[0] = take(rows * N * 4);
-  off[1] = take(rows * N * 4);
-  for (int i = 2; i < 6; ++i) off[i] = take(rows * 4);
-  off[6] = take((size_t)E * 4);
-  off[7] = take((size_t)E * 4);
-  return at;
+  Carver c{base};
+  w->U = c.take<float>(rows * N);
+  w->V = c.take<float>(rows * N);
+  w->CA = c.take<float>(rows);
+  w->rmax = c.take<float>(rows);
+  w->Q1 = c.take<float>(rows);
+  w->Q2 = c.take<float>(rows);
+  w->Ain = c.take<float>(E);
+  w->Aout = c.take<float>(E);
+  return c.bytes();
 }
 
 int sp_count_tiles(int B, int T, int E) {
@@ -670,28 +674,16 @@ int sp_count_tiles(int B, int T, int E) {
 template <int D, bool REG>
 hipError_t sp_vit_launch(const SpVitArgs& a, hipStream_t st) {
   const size_t lds = sp_vit_lds(a.N);
-  const hipError_t e = allow_lds(sp_vit_kernel<D, REG>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((sp_vit_kernel<D, REG>), dim3(a.B), dim3(sp_threads(a.N)), lds, st, a);
-  return hipGetLastError();
+  return launch(sp_vit_kernel<D, REG>, dim3(a.B), dim3(sp_threads(a.N)), lds, st, a);
 }
 
 template <int D>
 hipError_t sp_fb_launch(const SpFbArgs& a, bool rin, bool rout, hipStream_t st) {
   const size_t lds = sp_rows_lds(a.N);
   const dim3 grid(2 * a.B), block(sp_threads(a.N));
-#define HMM355_SP_FB(RI, RO)                                                   \
-  {                                                                            \
-    const hipError_t e = allow_lds(sp_fb_kernel<D, RI, RO>, lds);              \
-    if (e != hipSuccess) return e;                                             \
-    hipLaunchKernelGGL((sp_fb_kernel<D, RI, RO>), grid, block, lds, st, a);    \
-  }
-  if (rin && rout) HMM355_SP_FB(true, true)
-  else if (rin) HMM355_SP_FB(true, false)
-  else if (rout) HMM355_SP_FB(false, true)
-  else HMM355_SP_FB(false, false)
-#undef HMM355_SP_FB
-  return hipGetLastError();
+  return with_flag(rin, [&](auto ri) {
+    return with_flag(rout, [&](auto ro) { return launch(sp_fb_kernel<D, ri(), ro()>, grid, block, lds, st, a); });
+  });
 }
 
 int sp_slots(int N) {
@@ -730,20 +722,18 @@ HMM355_API int hmm355_sparse_viterbi_f32(const float* log_obs, const int* in_ptr
               static_cast<uint16_t*>(workspace), B, T, N, E, NB, (int)(sp_vit_lds(N) / ((size_t)NB * 2))};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool reg = maxdeg <= sp_reg_budget(N);
-  hipError_t e;
   switch (sp_slots(N)) {
-    case 1: e = reg ? sp_vit_launch<1, true>(a, st) : sp_vit_launch<1, false>(a, st); break;
-    case 2: e = reg ? sp_vit_launch<2, true>(a, st) : sp_vit_launch<2, false>(a, st); break;
-    case 4: e = reg ? sp_vit_launch<4, true>(a, st) : sp_vit_launch<4, false>(a, st); break;
-    default: e = reg ? sp_vit_launch<8, true>(a, st) : sp_vit_launch<8, false>(a, st); break;
+    case 1: return reg ? sp_vit_launch<1, true>(a, st) : sp_vit_launch<1, false>(a, st);
+    case 2: return reg ? sp_vit_launch<2, true>(a, st) : sp_vit_launch<2, false>(a, st);
+    case 4: return reg ? sp_vit_launch<4, true>(a, st) : sp_vit_launch<4, false>(a, st);
+    default: return reg ? sp_vit_launch<8, true>(a, st) : sp_vit_launch<8, false>(a, st);
   }
-  return e == hipSuccess ? HMM355_OK : (int)e;
 }
 
 HMM355_API size_t hmm355_sparse_forward_backward_workspace_bytes(int B, int T, int N, int E) {
   if (sp_check_shape(B, T, N, E) != HMM355_OK) return 0;
-  size_t off[kSpFbPieces];
-  return sp_fb_layout(B, T, N, E, off);
+  SpFbWs w;
+  return sp_fb_layout(B, T, N, E, nullptr, &w);
 }
 
 HMM355_API int hmm355_sparse_forward_backward_f32(const float* log_obs, const int* in_ptr_host, const int* in_ptr,
@@ -763,43 +753,25 @@ HMM355_API int hmm355_sparse_forward_backward_f32(const float* log_obs, const in
   if (rc != HMM355_OK) return rc;
   rc = sp_check_ptr(out_ptr_host, N, E, &dout);
   if (rc != HMM355_OK) return rc;
-  size_t off[kSpFbPieces];
-  if (workspace_bytes < sp_fb_layout(B, T, N, E, off)) return HMM355_E_WORKSPACE;
-  char* base = static_cast<char*>(workspace);
-  auto piece = [&](int i) { return reinterpret_cast<float*>(base + off[i]); };
+  SpFbWs w;
+  if (workspace_bytes < sp_fb_layout(B, T, N, E, static_cast<char*>(workspace), &w)) return HMM355_E_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t rows = (size_t)B * T;
-  hipError_t e;
-  {
-    size_t blocks = (rows + 3) / 4;
-    blocks = blocks < 4096 ? blocks : 4096;
-    hipLaunchKernelGGL(sp_row_max_kernel, dim3((unsigned)blocks), dim3(256), 0, st, log_obs, lengths, T, N, rows,
-                       piece(3));
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(sp_exp_kernel, dim3((E + 255) / 256), dim3(256), 0, st, in_log_w, out_log_w, piece(6),
-                       piece(7), E);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  }
-  SpFbArgs a{log_obs, {in_ptr, in_src, piece(6)}, {out_ptr, out_dst, piece(7)}, log_p0, lengths,
-             piece(3), piece(0), piece(1), piece(2), B, T, N, E};
+  HMM355_TRY(launch(sp_row_max_kernel, dim3(row_grid(rows, 4096)), dim3(256), 0, st, log_obs, lengths, T, N, rows,
+                    w.rmax));
+  HMM355_TRY(launch(sp_exp_kernel, dim3((E + 255) / 256), dim3(256), 0, st, in_log_w, out_log_w, w.Ain, w.Aout, E));
+  SpFbArgs a{log_obs, {in_ptr, in_src, w.Ain}, {out_ptr, out_dst, w.Aout}, log_p0, lengths,
+             w.rmax, w.U, w.V, w.CA, B, T, N, E};
   const bool rin = din <= sp_reg_budget(N), rout = dout <= sp_reg_budget(N);
   switch (sp_slots(N)) {
-    case 1: e = sp_fb_launch<1>(a, rin, rout, st); break;
-    case 2: e = sp_fb_launch<2>(a, rin, rout, st); break;
-    case 4: e = sp_fb_launch<4>(a, rin, rout, st); break;
-    default: e = sp_fb_launch<8>(a, rin, rout, st); break;
+    case 1: HMM355_TRY(sp_fb_launch<1>(a, rin, rout, st)); break;
+    case 2: HMM355_TRY(sp_fb_launch<2>(a, rin, rout, st)); break;
+    case 4: HMM355_TRY(sp_fb_launch<4>(a, rin, rout, st)); break;
+    default: HMM355_TRY(sp_fb_launch<8>(a, rin, rout, st)); break;
   }
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sp_scan_kernel, dim3(B), dim3(256), 0, st, piece(0), piece(2), piece(3), lengths, T, N, loglik);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  {
-    size_t blocks = (rows + 3) / 4;
-    blocks = blocks < 8192 ? blocks : 8192;
-    hipLaunchKernelGGL(sp_post_kernel, dim3((unsigned)blocks), dim3(256), 0, st, piece(0), piece(1), lengths, B, T, N,
-                       piece(4), piece(5), posterior);
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  HMM355_TRY(launch(sp_scan_kernel, dim3(B), dim3(256), 0, st, w.U, w.CA, w.rmax, lengths, T, N, loglik));
+  return launch(sp_post_kernel, dim3(row_grid(rows, 8192)), dim3(256), 0, st, w.U, w.V, lengths, B, T, N, w.Q1, w.Q2,
+                posterior);
 }
 
 HMM355_API size_t hmm355_sparse_arc_counts_workspace_bytes(int B, int T, int N, int E) {
@@ -817,19 +789,14 @@ HMM355_API int hmm355_sparse_arc_counts_f32(const float* log_obs, const int* src
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (B == 0) return HMM355_OK;
   if (!log_obs || !src || !dst || !log_w || !fb_workspace || !workspace) return HMM355_E_ARG;
-  size_t off[kSpFbPieces];
-  if (fb_workspace_bytes < sp_fb_layout(B, T, N, E, off)) return HMM355_E_WORKSPACE;
+  SpFbWs w;  // (read only here)
+  char* fb = const_cast<char*>(static_cast<const char*>(fb_workspace));
+  if (fb_workspace_bytes < sp_fb_layout(B, T, N, E, fb, &w)) return HMM355_E_WORKSPACE;
   const int tiles = sp_count_tiles(B, T, E);
   if (workspace_bytes < align_up((size_t)tiles * E * 8, 256)) return HMM355_E_WORKSPACE;
-  const char* base = static_cast<const char*>(fb_workspace);
-  auto piece = [&](int i) { return reinterpret_cast<const float*>(base + off[i]); };
   const long long rows = (long long)B * T;
-  SpCntArgs a{log_obs, src, dst, log_w, weight, lengths, piece(0), piece(1), piece(2), piece(3), piece(4), piece(5),
+  SpCntArgs a{log_obs, src, dst, log_w, weight, lengths, w.U, w.V, w.CA, w.rmax, w.Q1, w.Q2,
               static_cast<double*>(workspace), B, T, N, E, (rows + tiles - 1) / tiles};
-  hipLaunchKernelGGL(sp_count_kernel, dim3((E + 255) / 256, tiles), dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sp_count_sum_kernel, dim3((E + 255) / 256), dim3(256), 0, st, a.part, tiles, E, xi);
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  HMM355_TRY(launch(sp_count_kernel, dim3((E + 255) / 256, tiles), dim3(256), 0, st, a));
+  return launch(sp_count_sum_kernel, dim3((E + 255) / 256), dim3(256), 0, st, a.part, tiles, E, xi);
 }

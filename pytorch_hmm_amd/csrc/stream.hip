@@ -18,7 +18,7 @@
 // are KM x NJ registers and one 64-bit mask).
 // stream_beam_path_kernel walks the stored back-pointers from the best hypothesis (separate
 // launch: it reads what the forward kernel wrote).
-#include "common.h"
+#include "launch.h"
 
 #pragma clang fp contract(off)
 
@@ -232,10 +232,6 @@ __global__ void __launch_bounds__(64) stream_beam_path_kernel(BeamArgs a) {
 
 using namespace hmm355;
 
-static hipError_t st_lds(const void* k, int N) {
-  return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st_lds_bytes(N));
-}
-
 HMM355_API int hmm355_stream_greedy_f32(const float* emis, const float* log_T, const int* prev_state, float log_n,
                                         int B, int T, int N, int64_t* states, float* scores, void* stream) {
   if (B < 0 || T < 0 || N < 0) return HMM355_E_ARG;
@@ -243,12 +239,8 @@ HMM355_API int hmm355_stream_greedy_f32(const float* emis, const float* log_T, c
   if (B == 0 || T == 0) return HMM355_OK;
   if (!emis || !log_T || !prev_state || !states || !scores) return HMM355_E_ARG;
   auto kern = N <= kWave ? stream_greedy_kernel<1> : (N <= 2 * kWave ? stream_greedy_kernel<2> : stream_greedy_kernel<4>);
-  hipError_t e = st_lds(reinterpret_cast<const void*>(kern), N);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(B), dim3(256), st_lds_bytes(N), static_cast<hipStream_t>(stream),
-                     emis, log_T, prev_state, log_n, T, N, states, scores);
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return launch(kern, dim3(B), dim3(256), st_lds_bytes(N), static_cast<hipStream_t>(stream), emis, log_T, prev_state,
+                log_n, T, N, states, scores);
 }
 
 HMM355_API int hmm355_stream_beam_f32(const float* emis, const float* log_T, int B, int T, int N, int K,
@@ -278,12 +270,6 @@ HMM355_API int hmm355_stream_beam_f32(const float* emis, const float* log_T, int
     case 408: kern = stream_beam_kernel<4, 8>; break;
     default: kern = stream_beam_kernel<4, 16>; break;
   }
-  hipError_t e = st_lds(reinterpret_cast<const void*>(kern), N);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(B), dim3(256), st_lds_bytes(N), st, ba);
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(stream_beam_path_kernel, dim3(B), dim3(64), 0, st, ba);
-  e = hipGetLastError();
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  HMM355_TRY(launch(kern, dim3(B), dim3(256), st_lds_bytes(N), st, ba));
+  return launch(stream_beam_path_kernel, dim3(B), dim3(64), 0, st, ba);
 }

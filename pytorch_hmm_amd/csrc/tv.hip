@@ -784,28 +784,18 @@ struct TvFbWs {
 };
 static size_t tv_fb_ws_layout(int B, int T, int N, char* base, TvFbWs* w) {
   const size_t NP = pad_states(N), rows = (size_t)B * T;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t oU = take(2 * rows * NP * sizeof(float));   // U | V (post.h expects V = U + rows*NP)
-  const size_t oL = take(2 * rows * sizeof(float));        // LA | LB
-  const size_t oE = take(rows * NP * sizeof(float));
-  const size_t oM = take(rows * sizeof(float));
-  const size_t oC = take(2 * rows * sizeof(float));        // CA | CB
-  const size_t oI = take((size_t)B * NP * sizeof(float));   // terminal vector (adjoint)
-  const size_t oS = take((size_t)B * sizeof(float));
-  if (w && base) {
-    w->U = reinterpret_cast<float*>(base + oU);
-    w->V = w->U + rows * NP;
-    w->LA = reinterpret_cast<float*>(base + oL);
-    w->LB = w->LA + rows;
-    w->E = reinterpret_cast<float*>(base + oE);
-    w->M = reinterpret_cast<float*>(base + oM);
-    w->CA = reinterpret_cast<float*>(base + oC);
-    w->CB = w->CA + rows;
-    w->binit = reinterpret_cast<float*>(base + oI);
-    w->bscale = reinterpret_cast<float*>(base + oS);
-  }
-  return off;
+  Carver c{base};
+  w->U = c.take<float>(rows * NP);
+  w->V = c.take<float>(rows * NP);  // (post.h expects V = U + rows*NP: NP is a multiple of 64)
+  w->LA = c.take<float>(2 * rows);  // LA | LB
+  w->LB = w->LA ? w->LA + rows : nullptr;
+  w->E = c.take<float>(rows * NP);
+  w->M = c.take<float>(rows);
+  w->CA = c.take<float>(2 * rows);  // CA | CB
+  w->CB = w->CA ? w->CA + rows : nullptr;
+  w->binit = c.take<float>((size_t)B * NP);  // terminal vector (adjoint)
+  w->bscale = c.take<float>(B);
+  return c.bytes();
 }
 
 static bool tv_vec_ok(const float* lA, long long sb, long long st, int N) {
@@ -816,55 +806,26 @@ template <int NP>
 static hipError_t launch_tv_fb(const TvArgs& fa, const TvArgs& fb, const PostArgs& pa, const TvFbWs& w,
                                float* loglik, const float* bscale, bool vec, hipStream_t st) {
   const size_t rows = (size_t)fa.B * fa.T;
-  {
-    const size_t waves = rows < 16384 ? rows : 16384;
-    hipLaunchKernelGGL(tv_emis_kernel<NP>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, fa.lo, w.E, w.M,
-                       rows, fa.N);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipError_t e;
-  if (vec) {
-    e = allow_lds(tv_fb_kernel<NP, true>, kExclusiveLds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((tv_fb_kernel<NP, true>), dim3(2 * fa.B), dim3(512), kExclusiveLds, st, fa, fb);
-  } else {
-    e = allow_lds(tv_fb_kernel<NP, false>, kExclusiveLds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((tv_fb_kernel<NP, false>), dim3(2 * fa.B), dim3(512), kExclusiveLds, st, fa, fb);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(tv_scan_kernel, dim3(2 * fa.B), dim3(64), 0, st, w.CA, w.CB, w.M, w.LA, w.LB, loglik, bscale,
-                     fa.T);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  const size_t ewaves = rows < 16384 ? rows : 16384;
+  HMM355_TRY(launch(tv_emis_kernel<NP>, dim3((unsigned)((ewaves + 3) / 4)), dim3(256), 0, st, fa.lo, w.E, w.M, rows,
+                    fa.N));
+  HMM355_TRY(with_flag(vec, [&](auto v) {
+    return launch(tv_fb_kernel<NP, v()>, dim3(2 * fa.B), dim3(512), kExclusiveLds, st, fa, fb);
+  }));
+  HMM355_TRY(launch(tv_scan_kernel, dim3(2 * fa.B), dim3(64), 0, st, w.CA, w.CB, w.M, w.LA, w.LB, loglik, bscale,
+                    fa.T));
   const size_t waves = rows < 8192 ? rows : 8192;
-  hipLaunchKernelGGL(fb_posterior_kernel<NP>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, pa);
-  return hipGetLastError();
+  return launch(fb_posterior_kernel<NP>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, pa);
 }
 
 template <int NP>
 static hipError_t launch_tv_vit(const TvArgs& ta, const VitArgs& va, bool vec, hipStream_t st) {
-  hipError_t e;
-  if (vec) {
-    e = allow_lds(tv_vit_kernel<NP, true>, kExclusiveLds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((tv_vit_kernel<NP, true>), dim3(ta.B), dim3(512), kExclusiveLds, st, ta);
-  } else {
-    e = allow_lds(tv_vit_kernel<NP, false>, kExclusiveLds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((tv_vit_kernel<NP, false>), dim3(ta.B), dim3(512), kExclusiveLds, st, ta);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(tv_chunkmap_kernel<NP>, dim3(va.nchunks, va.B), dim3(NP), 0, st, va);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(vit_backtrace_kernel<NP>, dim3(va.nchunks, va.B), dim3(64), 0, st, va);
-  return hipGetLastError();
+  HMM355_TRY(with_flag(vec, [&](auto v) {
+    return launch(tv_vit_kernel<NP, v()>, dim3(ta.B), dim3(512), kExclusiveLds, st, ta);
+  }));
+  HMM355_TRY(launch(tv_chunkmap_kernel<NP>, dim3(va.nchunks, va.B), dim3(NP), 0, st, va));
+  return launch(vit_backtrace_kernel<NP>, dim3(va.nchunks, va.B), dim3(64), 0, st, va);
 }
-
 
 }  // namespace hmm355
 
@@ -872,7 +833,8 @@ using namespace hmm355;
 
 HMM355_API size_t hmm355_tv_fb_workspace_bytes(int B, int T, int N) {
   if (B < 0 || T < 1 || N < 1 || N > 256) return 0;
-  return tv_fb_ws_layout(B, T, N, nullptr, nullptr);
+  TvFbWs w;
+  return tv_fb_ws_layout(B, T, N, nullptr, &w);
 }
 
 HMM355_API int hmm355_tv_forward_backward_ex_f32(const float* log_obs, const float* log_A, long long a_bstride,
@@ -896,14 +858,8 @@ HMM355_API int hmm355_tv_forward_backward_ex_f32(const float* log_obs, const flo
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float* binit = nullptr;
   const float* bscale = nullptr;
-  if (log_beta_T) {  // the same terminal-vector preparation as fb.hip
-    switch (NP) {
-      case 64: hipLaunchKernelGGL(beta_init_kernel<64>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-      case 128: hipLaunchKernelGGL(beta_init_kernel<128>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-      default: hipLaunchKernelGGL(beta_init_kernel<256>, dim3(B), dim3(64), 0, st, log_beta_T, N, w.binit, w.bscale); break;
-    }
-    const hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess) return (int)e0;
+  if (log_beta_T) {
+    HMM355_TRY(launch_beta_init(NP, B, log_beta_T, N, w.binit, w.bscale, st));
     binit = w.binit;
     bscale = w.bscale;
   }
@@ -911,13 +867,7 @@ HMM355_API int hmm355_tv_forward_backward_ex_f32(const float* log_obs, const flo
   TvArgs fb{log_obs, log_A, a_bstride, a_tstride, log_p0, w.E, w.V, w.CB, nullptr, binit, B, T, N};
   PostArgs pa{w.U, w.V, w.LA, w.LB, posterior, forward, backward, lik_ref, B, T, N, out_mask};
   const bool vec = tv_vec_ok(log_A, a_bstride, a_tstride, N);
-  hipError_t e;
-  switch (NP) {
-    case 64: e = launch_tv_fb<64>(fa, fb, pa, w, loglik, bscale, vec, st); break;
-    case 128: e = launch_tv_fb<128>(fa, fb, pa, w, loglik, bscale, vec, st); break;
-    default: e = launch_tv_fb<256>(fa, fb, pa, w, loglik, bscale, vec, st); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(NP, [&](auto np) { return launch_tv_fb<np()>(fa, fb, pa, w, loglik, bscale, vec, st); });
 }
 
 HMM355_API int hmm355_tv_forward_backward_f32(const float* log_obs, const float* log_A, long long a_bstride,
@@ -955,13 +905,7 @@ HMM355_API int hmm355_tv_viterbi_f32(const float* log_obs, const float* log_A, l
   VitArgs va{log_obs, log_A, init, log_delta, nullptr, states, psi, G, B, T, N, HMM355_OBS_LOG, nc, nullptr};
   const bool vec = tv_vec_ok(log_A, a_bstride, a_tstride, N);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  switch (NP) {
-    case 64: e = launch_tv_vit<64>(ta, va, vec, st); break;
-    case 128: e = launch_tv_vit<128>(ta, va, vec, st); break;
-    default: e = launch_tv_vit<256>(ta, va, vec, st); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(NP, [&](auto np) { return launch_tv_vit<np()>(ta, va, vec, st); });
 }
 
 HMM355_API int hmm355_tv_fb_adjoint_f32(const float* E, const float* log_A, long long a_bstride, long long a_tstride,
@@ -977,17 +921,9 @@ HMM355_API int hmm355_tv_fb_adjoint_f32(const float* E, const float* log_A, long
   TvAdjArgs az{log_A, a_bstride, a_tstride, E, src_z, scale_z, P, B, T, N};
   const bool vec = tv_vec_ok(log_A, a_bstride, a_tstride, N);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipSuccess;
-  auto go = [&](auto kern) {
-    e = allow_lds(kern, kExclusiveLds);
-    if (e != hipSuccess) return;
-    hipLaunchKernelGGL(kern, dim3(2 * B), dim3(512), kExclusiveLds, st, aw, az);
-    e = hipGetLastError();
-  };
-  switch (pad_states(N)) {
-    case 64: vec ? go(tv_adjoint_kernel<64, true>) : go(tv_adjoint_kernel<64, false>); break;
-    case 128: vec ? go(tv_adjoint_kernel<128, true>) : go(tv_adjoint_kernel<128, false>); break;
-    default: vec ? go(tv_adjoint_kernel<256, true>) : go(tv_adjoint_kernel<256, false>); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(pad_states(N), [&](auto np) {
+    return with_flag(vec, [&](auto v) {
+      return launch(tv_adjoint_kernel<np(), v()>, dim3(2 * B), dim3(512), kExclusiveLds, st, aw, az);
+    });
+  });
 }

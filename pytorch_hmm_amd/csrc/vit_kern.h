@@ -327,12 +327,7 @@ __device__ __forceinline__ void vit_psi_follow(const RecArgs& ra, float* lds) {
 
 template <int NP>
 hipError_t launch_vit(const VitArgs& va, bool prep, hipStream_t sm) {
-  hipError_t e = allow_lds(vit_fwd_kernel<NP>, kExclusiveLds);  // own the CU (recur.h)
-  if (e != hipSuccess) return e;
-  if (va.band && prep) {
-    e = launch_band_prep(va.log_P, va.N, const_cast<BandDesc*>(va.band), sm);
-    if (e != hipSuccess) return e;
-  }
+  if (va.band && prep) HMM355_TRY(launch_band_prep(va.log_P, va.N, const_cast<BandDesc*>(va.band), sm));
   RecArgs ra{va.obs, va.log_P, va.init, va.delta, nullptr, nullptr, va.B, va.T, va.N, va.obs_mode, va.N, va.band,
              nullptr, nullptr, va.psi};
   ra.G = va.G;
@@ -347,30 +342,24 @@ hipError_t launch_vit(const VitArgs& va, bool prep, hipStream_t sm) {
     ra.path = va.path;
     ra.token = va.token;
     ra.vit_table = vit_follow_lds_bytes(va.T, NP, true) <= kExclusiveLds;
-    hipLaunchKernelGGL(vit_fwd_kernel<NP>, dim3(2 * va.B), dim3(kVitNT<NP>), kExclusiveLds, sm, ra);
-    return hipGetLastError();
+    return launch(vit_fwd_kernel<NP>, dim3(2 * va.B), dim3(kVitNT<NP>), kExclusiveLds, sm, ra);
   }
   // psi followers beside a dense chain (NP <= 128: the chain with block-work helpers publishes)
   const int nfollow = (NP <= 128 && va.prog && va.done) ? va.nfollow : 0;
   if (nfollow > 0) {
-    e = zero_words(va.prog, (size_t)va.B * kProgSlots * sizeof(int), sm);
-    if (e == hipSuccess) e = zero_words(va.done, (size_t)va.B * va.nchunks, sm);
-    if (e != hipSuccess) return e;
+    HMM355_TRY(zero_words(va.prog, (size_t)va.B * kProgSlots * sizeof(int), sm));
+    HMM355_TRY(zero_words(va.done, (size_t)va.B * va.nchunks, sm));
     ra.prog = va.prog;
     ra.done = va.done;
   }
-  hipLaunchKernelGGL(vit_fwd_kernel<NP>, dim3(va.B + nfollow), dim3(kVitNT<NP>), kExclusiveLds, sm, ra);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  // kExclusiveLds: the chain owns its CU (recur.h)
+  HMM355_TRY(launch(vit_fwd_kernel<NP>, dim3(va.B + nfollow), dim3(kVitNT<NP>), kExclusiveLds, sm, ra));
   // banded psi stages the chunk's delta rows in LDS (dynamic, kChunk x NP floats)
   const size_t psi_lds = va.band ? (size_t)kChunk * NP * sizeof(float) : 0;
   VitArgs vp = va;
   if (nfollow == 0) vp.done = nullptr;  // (no followers: every chunk here)
-  hipLaunchKernelGGL(vit_psi_kernel<NP>, dim3(va.nchunks, va.B), dim3(VF<NP>::NT), psi_lds, sm, vp);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(vit_backtrace_kernel<NP>, dim3(va.nchunks, va.B), dim3(64), 0, sm, va);
-  return hipGetLastError();
+  HMM355_TRY(launch(vit_psi_kernel<NP>, dim3(va.nchunks, va.B), dim3(VF<NP>::NT), psi_lds, sm, vp));
+  return launch(vit_backtrace_kernel<NP>, dim3(va.nchunks, va.B), dim3(64), 0, sm, va);
 }
 
 }  // namespace hmm355

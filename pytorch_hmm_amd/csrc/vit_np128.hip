@@ -20,10 +20,7 @@ HMM355_API int hmm355_debug_red_probe(const float* in, float* out, int n) {
   hipError_t e = hipMalloc(&din, ib);
   if (e == hipSuccess) e = hipMalloc(&dout, ob);
   if (e == hipSuccess) e = hipMemcpy(din, in, ib, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(hmm355::red_probe_kernel, dim3((n + 3) / 4), dim3(256), 0, 0, din, dout, n);
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess) e = hmm355::launch(hmm355::red_probe_kernel, dim3((n + 3) / 4), dim3(256), 0, 0, din, dout, n);
   if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
   (void)hipFree(din);
   (void)hipFree(dout);

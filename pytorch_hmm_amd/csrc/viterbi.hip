@@ -142,13 +142,12 @@ static int viterbi_run(const float* obs, int obs_mode, const float* log_P, const
   BandDesc* band = plan ? static_cast<BandDesc*>(const_cast<void*>(plan)) : reinterpret_cast<BandDesc*>(bandp);
   VitArgs va{obs, log_P, init, log_delta, final_score, states, psi, G, B, T, N, obs_mode, nc, band};
   hipStream_t sm = static_cast<hipStream_t>(stream);
-  hipError_t e;
   if (vit_follow_ok(flags, plan, B, T, N)) {
     // one launch: the chains, and per sequence a workgroup that first forms log(x + 1e-8) of
     // the sequence's emissions ahead of its chain (OBS_PROB) and then composes the chunk maps and
     // backtraces the path (follow.h).  The counts, one per 128-B line, zeroed first: [0, B) the
     // published psi blocks, [B, 2B) the leaders' blocks.
-    if ((e = prepare_counts(counts, (size_t)2 * B * kPubStride * sizeof(int), sm, &va.token)) != hipSuccess) return (int)e;
+    HMM355_TRY(prepare_counts(counts, (size_t)2 * B * kPubStride * sizeof(int), sm, &va.token));
     va.pub = counts;
     va.path = path;
     if (obs_mode == HMM355_OBS_PROB) {
@@ -156,11 +155,7 @@ static int viterbi_run(const float* obs, int obs_mode, const float* log_P, const
       va.lready = counts + (size_t)B * kPubStride;
     }
     va.nfollow = B;
-    switch (NP) {
-      case 128: e = launch_vit<128>(va, false, sm); break;
-      default: e = launch_vit<256>(va, false, sm); break;
-    }
-    return e == hipSuccess ? HMM355_OK : (int)e;
+    return NP == 128 ? launch_vit<128>(va, false, sm) : launch_vit<256>(va, false, sm);
   }
   // psi followers: the caller's word that the plan is dense, N <= 128, and CUs beside the chain.
   // A chain publishes a 64-step chunk every ~17 us (dense step ~270 ns) and a follower takes
@@ -182,17 +177,11 @@ static int viterbi_run(const float* obs, int obs_mode, const float* log_P, const
     size_t blocks = (n / 4 + 255) / 256;
     blocks = blocks < 8192 ? (blocks > 0 ? blocks : 1) : 8192;
     const int vec = (reinterpret_cast<uintptr_t>(obs) & 15) == 0;  // (lobuf is 256-B aligned)
-    hipLaunchKernelGGL(vit_log_obs_kernel, dim3((unsigned)blocks), dim3(256), 0, sm, obs, lobuf, n, vec);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    HMM355_TRY(launch(vit_log_obs_kernel, dim3((unsigned)blocks), dim3(256), 0, sm, obs, lobuf, n, vec));
     va.obs = lobuf;
     va.obs_mode = HMM355_OBS_LOG;
   }
-  switch (NP) {
-    case 64: e = launch_vit<64>(va, plan == nullptr, sm); break;
-    case 128: e = launch_vit<128>(va, plan == nullptr, sm); break;
-    default: e = launch_vit<256>(va, plan == nullptr, sm); break;
-  }
-  return e == hipSuccess ? HMM355_OK : (int)e;
+  return with_np(NP, [&](auto np) { return launch_vit<np()>(va, plan == nullptr, sm); });
 }
 
 HMM355_API int hmm355_viterbi_plan_ex_f32(const float* obs, int obs_mode, const float* log_P, const float* init,

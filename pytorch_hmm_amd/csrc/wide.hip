@@ -29,7 +29,7 @@
 // backward step reads coalesced rows too and one step kernel serves both directions
 // (blockIdx.z).  An epilogue accumulates the log-scales per sequence in fp64 and forms
 // posterior / forward / backward / loglik / lik_ref in one pass over (B,T,N).
-#include "common.h"
+#include "launch.h"
 #include "logcr.h"
 
 namespace hmm355 {
@@ -494,41 +494,23 @@ struct WFbWs {
 };
 size_t wide_fb_layout(int B, int T, int N, char* base, WFbWs* w) {
   const size_t rows = (size_t)B * T;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t oA = take((size_t)N * N * sizeof(float));
-  const size_t oAT = take((size_t)N * N * sizeof(float));
-  const size_t oU = take(rows * N * sizeof(float));
-  const size_t oV = take(rows * N * sizeof(float));
-  const size_t oSA = take(rows * sizeof(float));
-  const size_t oSB = take(rows * sizeof(float));
-  const size_t oM = take(rows * sizeof(float));
-  const size_t oCA = take(rows * sizeof(double));
-  const size_t oCB = take(rows * sizeof(double));
-  if (w && base) {
-    w->A = reinterpret_cast<float*>(base + oA);
-    w->AT = reinterpret_cast<float*>(base + oAT);
-    w->U = reinterpret_cast<float*>(base + oU);
-    w->V = reinterpret_cast<float*>(base + oV);
-    w->SA = reinterpret_cast<float*>(base + oSA);
-    w->SB = reinterpret_cast<float*>(base + oSB);
-    w->M = reinterpret_cast<float*>(base + oM);
-    w->CLA = reinterpret_cast<double*>(base + oCA);
-    w->CLB = reinterpret_cast<double*>(base + oCB);
-  }
-  return off;
+  Carver c{base};
+  w->A = c.take<float>((size_t)N * N);
+  w->AT = c.take<float>((size_t)N * N);
+  w->U = c.take<float>(rows * N);
+  w->V = c.take<float>(rows * N);
+  w->SA = c.take<float>(rows);
+  w->SB = c.take<float>(rows);
+  w->M = c.take<float>(rows);
+  w->CLA = c.take<double>(rows);
+  w->CLB = c.take<double>(rows);
+  return c.bytes();
 }
 
 }  // namespace
 }  // namespace hmm355
 
 using namespace hmm355;
-
-#define WIDE_LAUNCHED()                              \
-  do {                                               \
-    const hipError_t e_ = hipGetLastError();         \
-    if (e_ != hipSuccess) return (int)e_;            \
-  } while (0)
 
 HMM355_API size_t hmm355_viterbi_wide_workspace_bytes(int B, int T, int N, int obs_mode) {
   if (B < 0 || T < 1 || N < 1 || N > kWideMaxN) return 0;
@@ -554,26 +536,22 @@ HMM355_API int hmm355_viterbi_wide_f32(const float* obs, int obs_mode, const flo
     float* lobuf = reinterpret_cast<float*>(static_cast<char*>(workspace) +
                                             align_up((size_t)B * T * N * sizeof(uint16_t), 256));
     const size_t n = (size_t)B * T * N;
-    hipLaunchKernelGGL(wide_log_obs_kernel, dim3(stride_blocks(n, 8192)), dim3(256), 0, sm, obs, lobuf, n);
-    WIDE_LAUNCHED();
+    HMM355_TRY(launch(wide_log_obs_kernel, dim3(stride_blocks(n, 8192)), dim3(256), 0, sm, obs, lobuf, n));
     lo = lobuf;
   }
   WVitArgs a{lo, log_P, log_delta, psi, B, T, N};
-  hipLaunchKernelGGL(wide_vit_init_kernel, dim3(stride_blocks((size_t)B * N, 4096)), dim3(256), 0, sm, a, init);
-  WIDE_LAUNCHED();
+  HMM355_TRY(launch(wide_vit_init_kernel, dim3(stride_blocks((size_t)B * N, 4096)), dim3(256), 0, sm, a, init));
   const dim3 grid((N + kColTile - 1) / kColTile, (B + kBT - 1) / kBT);
   for (int t = 1; t < T; ++t) {
-    hipLaunchKernelGGL(wide_vit_step_kernel, grid, dim3(kStepThreads), 0, sm, a, t);
-    WIDE_LAUNCHED();
+    HMM355_TRY(launch(wide_vit_step_kernel, grid, dim3(kStepThreads), 0, sm, a, t));
   }
-  hipLaunchKernelGGL(wide_backtrace_kernel, dim3(B), dim3(256), 0, sm, a, states, final_score);
-  WIDE_LAUNCHED();
-  return HMM355_OK;
+  return launch(wide_backtrace_kernel, dim3(B), dim3(256), 0, sm, a, states, final_score);
 }
 
 HMM355_API size_t hmm355_fb_wide_workspace_bytes(int B, int T, int N) {
   if (B < 0 || T < 1 || N < 1 || N > kWideMaxN) return 0;
-  return wide_fb_layout(B, T, N, nullptr, nullptr);
+  WFbWs w;
+  return wide_fb_layout(B, T, N, nullptr, &w);
 }
 
 HMM355_API int hmm355_forward_backward_wide_f32(const float* obs, int obs_mode, const float* log_P,
@@ -596,29 +574,24 @@ HMM355_API int hmm355_forward_backward_wide_f32(const float* obs, int obs_mode, 
   WFbWs w;
   wide_fb_layout(B, T, N, static_cast<char*>(workspace), &w);
   const size_t rows = (size_t)B * T;
-  hipLaunchKernelGGL(wide_exp_matrix_kernel, dim3(stride_blocks((size_t)N * N, 4096)), dim3(256), 0, sm, log_P, N, w.A,
-                     w.AT);
-  WIDE_LAUNCHED();
+  HMM355_TRY(launch(wide_exp_matrix_kernel, dim3(stride_blocks((size_t)N * N, 4096)), dim3(256), 0, sm, log_P, N, w.A,
+                    w.AT));
   if (obs_mode == HMM355_OBS_LOG) {
-    hipLaunchKernelGGL(wide_row_max_kernel, dim3(stride_blocks(rows * 64, 4096)), dim3(256), 0, sm, obs, N, rows, w.M);
-    WIDE_LAUNCHED();
+    HMM355_TRY(launch(wide_row_max_kernel, dim3(stride_blocks(rows * 64, 4096)), dim3(256), 0, sm, obs, N, rows,
+                      w.M));
   }
   WFbArgs a{obs, w.M, w.A, w.AT, w.U, w.V, w.SA, w.SB, B, T, N, obs_mode};
-  hipLaunchKernelGGL(wide_fb_init_kernel, dim3(stride_blocks((size_t)B * N, 4096)), dim3(256), 0, sm, a, log_p0);
-  WIDE_LAUNCHED();
+  HMM355_TRY(launch(wide_fb_init_kernel, dim3(stride_blocks((size_t)B * N, 4096)), dim3(256), 0, sm, a, log_p0));
   const dim3 grid((N + kColTile - 1) / kColTile, (B + kBT - 1) / kBT, 2);
   for (int k = 1; k < T; ++k) {
-    hipLaunchKernelGGL(wide_fb_step_kernel, grid, dim3(kStepThreads), 0, sm, a, k);
-    WIDE_LAUNCHED();
+    HMM355_TRY(launch(wide_fb_step_kernel, grid, dim3(kStepThreads), 0, sm, a, k));
   }
-  hipLaunchKernelGGL(wide_scan_kernel, dim3(B), dim3(256), 0, sm, a, w.CLA, w.CLB, loglik);
-  WIDE_LAUNCHED();
+  HMM355_TRY(launch(wide_scan_kernel, dim3(B), dim3(256), 0, sm, a, w.CLA, w.CLB, loglik));
   const unsigned mask = out_mask & (HMM355_FB_POSTERIOR | HMM355_FB_FORWARD | HMM355_FB_BACKWARD);
   if (mask || lik_ref) {
     const size_t visits = mask ? rows : (size_t)B;
-    hipLaunchKernelGGL(wide_post_kernel, dim3(stride_blocks(visits * 64, 8192)), dim3(256), 0, sm, a, w.CLA, w.CLB, mask,
-                       posterior, forward, backward, lik_ref);
-    WIDE_LAUNCHED();
+    HMM355_TRY(launch(wide_post_kernel, dim3(stride_blocks(visits * 64, 8192)), dim3(256), 0, sm, a, w.CLA, w.CLB,
+                      mask, posterior, forward, backward, lik_ref));
   }
   return HMM355_OK;
 }
