@@ -59,6 +59,12 @@ typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned 
 constexpr int emis_ahead(int kind) {
   return kind == kFbAlpha ? HMM355_EMIS_AHEAD_ALPHA : kind == kFbBeta ? HMM355_EMIS_AHEAD_BETA : HMM355_EMIS_AHEAD_VIT;
 }
+// HMM355_BLOCK_EDGE: 0 builds rec_band's chains with the block loop of round 11 (diagnostic
+// builds: the parent's figures from this tree, tools/band_stamps.py)
+#ifndef HMM355_BLOCK_EDGE
+#define HMM355_BLOCK_EDGE 1
+#endif
+constexpr bool kBlockEdge = HMM355_BLOCK_EDGE;
 // The form of the step's wave reduction (wave_red_level) by chain: what measured faster per chain
 // (DESIGN section 14 round 11): beta and Viterbi both triples, alpha, whose reduction is not
 // filled, the first one.  HMM355_RED_FORM (common.h) sets all three, for diagnostic builds.
@@ -87,6 +93,10 @@ static __device__ unsigned long long g_rec_stamps[kStamp ? kStampWaves * 8 : 1];
 // HMM355_STAMP=2: also the staging helpers' block work by item and the psi waves (rec_band); these
 // stamps wait for the wave's LDS reads, so the chain's own figures are taken from a STAMP=1 build
 constexpr bool kStampItems = HMM355_STAMP > 1;
+#ifndef HMM355_STAMP_BAR
+#define HMM355_STAMP_BAR 1
+#endif
+constexpr bool kStampBar = HMM355_STAMP_BAR;  // (band_chain: stamps round the block barrier)
 
 template <int NP>
 struct RC {
@@ -1357,7 +1367,9 @@ constexpr int win_shift_term(int m, int NB, int NWIN, int TD0) {
 // kernel, fbpair.h): the whole recursion of one sequence in one wave, one lds_barrier per
 // 16-step block and one after the last row, matching the helpers' barriers.  `lds` is the
 // chain's own RC<NP> layout.
-template <int NP, int KIND, int WP, int TD0 = 0, int TW = 0, int EA = emis_ahead(KIND)>
+// EDGE: the loop over whole blocks of round 12 (run_edge below), whose barrier stands EA steps
+// before the block's end; rec_band's chains take it, the pair kernel's keep the loop they had.
+template <int NP, int KIND, int WP, int TD0 = 0, int TW = 0, int EA = emis_ahead(KIND), bool EDGE = false>
 __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, const BandDesc* __restrict__ d) {
   using C = RC<NP>;
   constexpr int NB = C::NBLK;
@@ -1653,10 +1665,23 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
   };
 
   // (diagnostic builds: cycles at the block barriers, the whole chain, and its real time)
-  unsigned long long st_bar = 0, st_t0 = 0;
+  // (the whole blocks by part: st_steady from the top of step 1 to behind step 15, st_edge the
+  // rest -- step 0 and whatever stands between two blocks; st_bar_in: the barrier wait that
+  // falls into steps 1 .. 15)
+  unsigned long long st_bar = 0, st_t0 = 0, st_steady = 0, st_edge = 0, st_nsteady = 0, st_nedge = 0, st_bar_in = 0;
   long long rt0 = 0;
   if (kStamp) { st_t0 = stamp(); rt0 = __builtin_amdgcn_s_memrealtime(); }
+  // (HMM355_STAMP_BAR=0: no stamps round the block barrier, whose pair stands inside steps 1 .. 15
+  // of the round-12 loop and costs them a stamp's latency; the barrier's wait is then in the part
+  // it stands in)
+  auto block_barrier = [&]() {
+    unsigned long long sb = 0;
+    if (kStamp && kStampBar) sb = stamp();
+    if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();
+    if (kStamp && kStampBar) st_bar += stamp() - sb;
+  };
   auto run_blocks = [&](auto UA) {
+    unsigned long long s15 = 0;
     for (int kb = 0; kb < nblocks; ++kb) {
       const int q0 = kb * 16 < 1 ? 1 : kb * 16;
       const int q1 = (kb + 1) * 16 < T ? (kb + 1) * 16 : T;
@@ -1675,11 +1700,21 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
         static_for<1, EA>([&](auto K) { ld(ebase + (decltype(K)::value - 1) * NP, en[decltype(K)::value]); });
         static_for<0, 16>([&](auto JJ) {
           constexpr int jj = decltype(JJ)::value;
+          if (kStamp && jj == 1) {
+            const unsigned long long s1 = stamp();
+            if (s15) { st_edge += s1 - s15; ++st_nedge; }
+            s15 = s1;
+          }
           step(kb * 16 + jj, jj, jj + EA > 15, UA, std::bool_constant<(jj > 0)>{}, std::bool_constant<(jj == 0)>{},
                std::integral_constant<int, jj % EA>{}, std::bool_constant<(EA == 2 && KIND != kFbAlpha && jj < 15)>{},
                jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + (jj + EA - 1) * NP, blk,
                [](float& d, float v) { writelane_c<jj>(d, v); });
         });
+        if (kStamp) {
+          const unsigned long long t = stamp();
+          st_steady += t - s15; ++st_nsteady;
+          s15 = t;
+        }
         // the block's normalisers / floor maxima: lane jj -> row 16kb + jj - 1 (entry 0 of its
         // 64-float slot, where rec_ls_scan / the psi waves / fbpair's scan read it)
         if constexpr (FB || FUSE) {
@@ -1695,17 +1730,113 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
                [sc](float&, float v) { *sc = v; });
         }
       }
-      unsigned long long sb = 0;
-      if (kStamp) sb = stamp();
-      if (!(kAbl & abl::kBandNoBlockBarrier)) lds_barrier();  // B_{kb+1}: block kb+1 staged by the helpers, rows of block kb-1 written
-      if (kStamp) st_bar += stamp() - sb;
+      block_barrier();  // B_{kb+1}: block kb+1 staged by the helpers, rows of block kb-1 written
     }
   };
+  // The same blocks with a hot loop that holds only whole ones (EDGE).
+  // Block 0 (no step 0) and a partial last block run rolled, as above.  The whole blocks 1 ..
+  // T / 16 - 1 run in a loop that tests its trip count and nothing else:
+  //  - its bases (emission slot, the next block's, row-ring slot, the wrapped row, the normaliser
+  //    word) advance by an add and a wrap each; no % 3, no multiply, no q0 / q1;
+  //  - the emission rotation runs on across the edge: step jj reads the row of step jj + EA, and
+  //    where that is a step of block kb + 1 it reads that block's slot, so a block starts with its
+  //    first EA rows in registers (beta's step 0 takes row 15 of the block before: still this
+  //    block's slot).  For that the wave meets its block barrier B_{kb+1} (block kb + 1 staged)
+  //    behind step 15 - EA, at the end of that step, when the step's own LDS operations have long
+  //    completed, and not behind step 15.  The helpers' and psi waves' barriers stand where they
+  //    stood: every wave still meets one barrier a block.
+  //    Why the two (EA) steps behind the barrier are safe:
+  //     * they write rows 16kb + 15 - EA .. 16kb + 14 and, behind step 15, the block's normaliser
+  //       words (rows 16kb - 1 .. 16kb + 14).  Whoever reads them works two blocks behind: the
+  //       helpers' block_work(k), between B_k and B_{k+1}, scans and flushes block k - 2
+  //       (rec_ls_scan: words 16(k-2) - 1 .. + 14; rec_flush: rows 16(k-2) .. + 15, the last of them
+  //       written by step 0 of block k - 1), the psi waves read rows and words 16(k-2) - 1 .. + 14.
+  //       Block kb's are read behind B_{kb+2}, which this wave meets a block later; the 64-row
+  //       rings hold four blocks, so what these steps overwrite is block kb - 4's, read behind
+  //       B_{kb-2};
+  //     * they read slot kb % 3 and slot (kb + 1) % 3 of the staging ring.  Behind B_{kb+1} the
+  //       helpers stage block kb + 2 into slot (kb + 2) % 3, which held block kb - 1: this wave
+  //       read its last row of it (beta's step 0 of block kb) a block ago.
+  //    Behind the last whole block the rows read across the edge are a partial block's (it reads
+  //    its own first row again behind its barrier) or the padding the helpers stage past the end:
+  //    inside the ring either way, and not used;
+  //  - every lane stores the block's normaliser register: lane jj < 16 to entry 0 of row
+  //    16kb + jj - 1's 64-word slot, as before, lanes 16 .. 63 to entries 1 .. 3 of the same slots,
+  //    which nobody reads.  One add and one and per block, no exec mask.
+  // Step 0's arithmetic (RL, plain_sum, rwrap) is what it was.
+  auto run_edge = [&](auto UA) {
+    auto rolled = [&](int kb, int q0, int q1) {
+      if (q0 < q1) ld(erow(q0 - EL), en[0]);
+      float* rbase = lds + C::OFF_RING + ((16 * kb) & (C::RING - 1)) * NP;
+      float* rwrap = lds + C::OFF_RING + ((16 * kb - 1) & (C::RING - 1)) * NP;
+      const float* ebase = lds + C::OFF_EMIS + ((kb % 3) * 16 + 1 - EL) * NP + NB * l;
+      float none = 0.f;
+      for (int q = q0; q < q1; ++q) {
+        const int jj = q - kb * 16;
+        float* sc = lds + C::OFF_SC + 64 * ((q - 1) & (C::RING - 1));
+        step(q, jj, q + 1 == q1, UA, std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}, std::false_type{},
+             jj == 0 ? rwrap : rbase + (jj - 1) * NP, ebase + jj * NP, none,
+             [sc](float&, float v) { *sc = v; });
+      }
+      block_barrier();
+    };
+    rolled(0, 1, T < 16 ? T : 16);
+    const int nfull = T / 16 - 1;  // whole blocks behind block 0
+    if (nfull > 0) {
+      // (behind B_1: block 1 is staged; the only rows of a whole block read at its top)
+      static_for<0, EA>([&](auto K) { ld(erow(16 + decltype(K)::value - EL), en[decltype(K)::value]); });
+      int es = 16 * NP, rb = 16 * NP;  // block 1's staging slot and first row, in floats
+      int scw = 64 * ((15 + (l & 15)) & (C::RING - 1)) + (l >> 4);
+      float blk = 0.f;
+      unsigned long long s15 = 0;
+      for (int kb = 1; kb <= nfull; ++kb) {
+        const int esn = es == 32 * NP ? 0 : es + 16 * NP;
+        float* rbase = lds + C::OFF_RING + rb;
+        float* rwrap = lds + C::OFF_RING + ((rb - NP) & (C::RING * NP - 1));
+        const float* ebase = lds + C::OFF_EMIS + es + (1 - EL) * NP + NB * l;
+        const float* nbase = lds + C::OFF_EMIS + esn + NB * l;
+        static_for<0, 16>([&](auto JJ) {
+          constexpr int jj = decltype(JJ)::value;
+          constexpr int p = jj + EA - EL;  // the row this step reads, counted from the block's slot
+          if (kStamp && jj == 1) {
+            const unsigned long long s1 = stamp();
+            if (s15) { st_edge += s1 - s15; ++st_nedge; }
+            s15 = s1;
+          }
+          step(kb * 16 + jj, jj, false, UA, std::bool_constant<(jj > 0)>{}, std::bool_constant<(jj == 0)>{},
+               std::integral_constant<int, jj % EA>{}, std::bool_constant<(EA == 2 && KIND != kFbAlpha)>{},
+               jj == 0 ? rwrap : rbase + (jj - 1) * NP, p < 16 ? ebase + (jj + EA - 1) * NP : nbase + (p - 16) * NP, blk,
+               [](float& d, float v) { writelane_c<jj>(d, v); });
+          if constexpr (jj == 15 - EA) {  // B_{kb+1}
+            const unsigned long long b0 = st_bar;
+            block_barrier();
+            st_bar_in += st_bar - b0;
+          }
+        });
+        if (kStamp) {
+          const unsigned long long t = stamp();
+          st_steady += t - s15; ++st_nsteady;
+          s15 = t;
+        }
+        if constexpr (FB || FUSE) {
+          lds[C::OFF_SC + scw] = blk;
+          scw = (scw + 16 * 64) & (C::RING * 64 - 1);
+        }
+        es = esn;
+        rb = (rb + 16 * NP) & (C::RING * NP - 1);
+      }
+    }
+    if (T > 16 && (T & 15)) rolled(T / 16, T & ~15, T);
+  };
+  auto run = [&](auto UA) {
+    if constexpr (EDGE) run_edge(UA);
+    else run_blocks(UA);
+  };
   if constexpr (KIND == kFbAlpha) {
-    if (uafl) run_blocks(std::true_type{});
-    else run_blocks(std::false_type{});
+    if (uafl) run(std::true_type{});
+    else run(std::false_type{});
   } else {
-    run_blocks(std::false_type{});
+    run(std::false_type{});
   }
   if (kStamp && l == 0) {
     const unsigned long long t1 = stamp();
@@ -1713,6 +1844,10 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     unsigned long long* o8 = g_rec_stamps + ((size_t)blockIdx.x * 16 % kStampWaves) * 8;
     o8[0] = (unsigned long long)rt0; o8[1] = (unsigned long long)rt1; o8[3] = st_bar;
     o8[4] = T; o8[5] = t1 - st_t0; o8[6] = t1 - st_t0; o8[7] = (unsigned long long)(rt1 - rt0);
+    // the whole blocks by part, in the record of wave 4 (which has ended): steps 1 .. 15, their
+    // count, the rest (step 0 and the edge), its count, the barrier wait inside steps 1 .. 15
+    unsigned long long* e8 = g_rec_stamps + (((size_t)blockIdx.x * 16 + 4) % kStampWaves) * 8;
+    e8[0] = st_steady; e8[1] = st_nsteady; e8[2] = st_edge; e8[3] = st_nedge; e8[4] = st_bar_in;
   }
   float* row = lds + C::OFF_RING + ((T - 1) & (C::RING - 1)) * NP;
   st(row + NB * l, y);
@@ -1799,7 +1934,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
   lds_barrier();
 
   if (w == 0) {
-    band_chain<NP, KIND, WP, TD0, TW>(a, lds, b, d);
+    band_chain<NP, KIND, WP, TD0, TW, emis_ahead(KIND), kBlockEdge>(a, lds, b, d);
     return;
   }
   // ---------------------------------------------------------------- helper waves
