@@ -32,16 +32,6 @@
 
 namespace hmm355 {
 
-template <int NP>
-struct AdjGeo {
-  static constexpr int NW = NP / 32;      // waves
-  static constexpr int NT = NW * kWave;   // threads
-  static constexpr int HALF = NP / 2;     // inputs per lane
-  static constexpr int XS = HALF + 4;     // LDS stride of an input half (the two half-wave
-                                          // broadcast addresses fall in different banks)
-  static constexpr int PD = 8;            // steps of loads in flight
-};
-
 struct AdjArgs {
   const float* E;      // (B,T,N) staged emissions
   const float* log_P;  // (N,N)
@@ -56,7 +46,7 @@ struct AdjArgs {
 
 template <int NP, int CH>
 __device__ __forceinline__ void adj_chain(const AdjArgs& a, int b, float* lds) {
-  using G = AdjGeo<NP>;
+  using G = ChainGeo<NP>;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   const int o = 32 * w + (l & 31), h = l >> 5;
   const int T = a.T, N = a.N;
@@ -137,8 +127,8 @@ __device__ __forceinline__ void adj_chain(const AdjArgs& a, int b, float* lds) {
 }
 
 template <int NP>
-__global__ void __launch_bounds__(AdjGeo<NP>::NT) fb_adjoint_kernel(AdjArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * AdjGeo<NP>::XS];
+__global__ void __launch_bounds__(ChainGeo<NP>::NT) fb_adjoint_kernel(AdjArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * ChainGeo<NP>::XS];
   const int b = blockIdx.x >> 1;
   if (blockIdx.x & 1) adj_chain<NP, 1>(a, b, lds);
   else adj_chain<NP, 0>(a, b, lds);
@@ -160,6 +150,6 @@ HMM355_API int hmm355_fb_adjoint_f32(const float* E, const float* log_P, const f
   AdjArgs a{E, log_P, src_w, scale_w, src_z, scale_z, W, P, B, T, N};
   hipStream_t st = static_cast<hipStream_t>(stream);
   return with_np(pad_states(N), [&](auto np) {
-    return launch(fb_adjoint_kernel<np()>, dim3(2 * B), dim3(AdjGeo<np()>::NT), 0, st, a);
+    return launch(fb_adjoint_kernel<np()>, dim3(2 * B), dim3(ChainGeo<np()>::NT), 0, st, a);
   });
 }

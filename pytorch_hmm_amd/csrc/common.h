@@ -220,6 +220,85 @@ __device__ __forceinline__ void wave_argmax_dpp(float& v, int& i) {
   i = ic;
 }
 
+// All-reduce over the `sub` lanes of a group (a power of two, aligned inside a wave), on DPP and
+// permlane swaps: quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror, then the row
+// pairs and the wave halves.  Every level pairs a lane with the lane that holds the other half's
+// value, so a lane and its partner combine the same two numbers: the result has the same bits in
+// every lane of the group.  (`sub` is uniform: the branches are scalar.)
+template <typename Op>
+__device__ __forceinline__ float grp_reduce(float v, int sub, Op op) {
+  if (sub >= 2) v = op(v, dpp_f<0xB1>(v));
+  if (sub >= 4) v = op(v, dpp_f<0x4E>(v));
+  if (sub >= 8) v = op(v, dpp_f<0x141>(v));
+  if (sub >= 16) v = op(v, dpp_f<0x140>(v));
+  if (sub >= 32) {
+    float a = v, b = v;
+    permlane16_swap(a, b);  // a = rows [0,0,2,2], b = rows [1,1,3,3]
+    v = op(a, b);
+  }
+  if (sub >= 64) {
+    float a = v, b = v;
+    permlane32_swap(a, b);
+    v = op(a, b);
+  }
+  return v;
+}
+__device__ __forceinline__ float grp_max_rt(float v, int sub) {
+  return grp_reduce(v, sub, [](float a, float b) { return fmaxf(a, b); });
+}
+__device__ __forceinline__ float grp_sum_rt(float v, int sub) {
+  return grp_reduce(v, sub, [](float a, float b) { return a + b; });
+}
+// its (value, index) form: the larger value, of equal values the smaller index
+__device__ __forceinline__ void grp_argmax_rt(float& v, int& i, int sub) {
+  if (sub >= 2) argmax_combine(v, i, dpp_f<0xB1>(v), dpp_i<0xB1>(i));
+  if (sub >= 4) argmax_combine(v, i, dpp_f<0x4E>(v), dpp_i<0x4E>(i));
+  if (sub >= 8) argmax_combine(v, i, dpp_f<0x141>(v), dpp_i<0x141>(i));
+  if (sub >= 16) argmax_combine(v, i, dpp_f<0x140>(v), dpp_i<0x140>(i));
+  if (sub >= 32) {
+    float a = v, b = v;
+    int ia = i, ib = i;
+    permlane16_swap(a, b);
+    permlane16_swap_i(ia, ib);
+    argmax_combine(a, ia, b, ib);
+    v = a;
+    i = ia;
+  }
+  if (sub >= 64) {
+    float a = v, b = v;
+    int ia = i, ib = i;
+    permlane32_swap(a, b);
+    permlane32_swap_i(ia, ib);
+    argmax_combine(a, ia, b, ib);
+    v = a;
+    i = ia;
+  }
+}
+
+// all-reduce over a compile-time SUB lanes (16: one DPP row; 8: half a row; 4: a quad)
+template <int SUB>
+__device__ __forceinline__ float grp_max(float v) {
+  v = fmaxf(v, dpp_f<0xB1>(v));                       // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_f<0x4E>(v));                       // quad_perm [2,3,0,1]
+  if constexpr (SUB == 8) v = fmaxf(v, dpp_f<0x141>(v));   // row_half_mirror
+  if constexpr (SUB == 16) {
+    v = fmaxf(v, dpp_f<0x124>(v));                    // row_ror:4
+    v = fmaxf(v, dpp_f<0x128>(v));                    // row_ror:8
+  }
+  return v;
+}
+template <int SUB>
+__device__ __forceinline__ int grp_min_i(int v) {
+  v = min(v, dpp_i<0xB1>(v));
+  v = min(v, dpp_i<0x4E>(v));
+  if constexpr (SUB == 8) v = min(v, dpp_i<0x141>(v));
+  if constexpr (SUB == 16) {
+    v = min(v, dpp_i<0x124>(v));
+    v = min(v, dpp_i<0x128>(v));
+  }
+  return v;
+}
+
 // Out of the fp32 range (hmm355.h, range contract) the chains can leave 0, denormals, inf and NaN
 // in their rows and log-scales.  What is formed from them afterwards -- the row passes' posterior,
 // forward and backward rows, the arc counts, the stored loglik -- must still be clean: a dead row
@@ -257,6 +336,53 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// workgroup reductions over NT threads through LDS (`red`: NT / 64 words): max of a float; min of
+// an int
+template <int NT>
+__device__ __forceinline__ float wg_max(float v, float* red) {
+  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = red[0];
+  for (int k = 1; k < NT / 64; ++k) r = fmaxf(r, red[k]);
+  return r;
+}
+template <int NT>
+__device__ __forceinline__ int wg_min(int v, int* red) {
+  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = red[0];
+  for (int k = 1; k < NT / 64; ++k) r = min(r, red[k]);
+  return r;
+}
+
+__device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// sequence b's length clamped to 1 .. T; no lengths: T
+template <typename I>  // (the index as the caller holds it: int or size_t)
+__device__ __forceinline__ int seq_len(const int* lengths, I b, int T) {
+  if (!lengths) return T;
+  return clamp_int(lengths[b], 1, T);
+}
+
+// log(e^a + e^b + e^c); -inf when all three are
+__device__ __forceinline__ float lse3(float a, float b, float c) {
+  const float m = fmaxf(fmaxf(a, b), c);
+  const float ms = m == -INFINITY ? 0.f : m;
+  const float s = expf(a - ms) + expf(b - ms) + expf(c - ms);
+  const float r = ms + logf(s);
+  return m == -INFINITY ? -INFINITY : r;
+}
+__device__ __forceinline__ float lse2(float a, float b) {
+  const float m = fmaxf(a, b);
+  const float ms = m == -INFINITY ? 0.f : m;
+  const float s = expf(a - ms) + expf(b - ms);
+  const float r = ms + logf(s);
+  return m == -INFINITY ? -INFINITY : r;
+}
+
 // Correctly rounded fp32 log(x + 1e-8f): the sum is formed in fp32 exactly as the
 // reference does (hmm.py:86), the log in fp64 then rounded once.  torch-CPU's logf agrees
 // with the correctly rounded value on all but ~2.5e-5 of softmax-distributed inputs.
@@ -277,6 +403,17 @@ __device__ __forceinline__ void step_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   else
     lds_barrier();
+}
+// workgroup barrier that also waits for the workgroup's global stores: behind it every thread
+// sees what any thread of the workgroup stored to memory before it
+__device__ __forceinline__ void global_barrier() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __threadfence_block();
+  __syncthreads();
+}
+// an L1-bypassing load (agent scope): rows that other waves of this workgroup wrote earlier
+__device__ __forceinline__ float ld_fresh(const float* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Allow a kernel more than the default 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU).
@@ -341,8 +478,45 @@ static __global__ void zero_words_kernel(unsigned* p, int n) {
 }
 // (its launcher zero_words and prepare_counts: launch.h)
 
+// The row maxima M_t = max_j lo_t[j] of log-emissions (B,T,N): one wave per (b,t) row,
+// grid-stride.  A row without a finite maximum gets M = 0 (its emissions stay exp(lo)).  RAGGED:
+// only frames t < seq_len(lengths, b, T) are read; a padded frame gets 0.
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) row_max_kernel(const float* __restrict__ lo, const int* __restrict__ lengths,
+                                                      int T, int N, size_t rows, float* __restrict__ m) {
+  const int l = threadIdx.x & 63;
+  const size_t nw = ((size_t)gridDim.x * blockDim.x) >> 6;
+  for (size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < rows; row += nw) {
+    bool valid = true;
+    if constexpr (RAGGED) {
+      const int b = (int)(row / T), t = (int)(row % T);
+      valid = t < seq_len(lengths, b, T);
+    }
+    float v = -INFINITY;
+    if (valid) {
+      const float* src = lo + row * N;
+      for (int j = l; j < N; j += 64) v = fmaxf(v, src[j]);
+      v = wave_max_dpp2(v);
+    }
+    if (l == 0) m[row] = (v > -INFINITY && v < INFINITY) ? v : 0.f;
+  }
+}
+
 inline int pad_states(int N) { return N <= 64 ? 64 : (N <= 128 ? 128 : 256); }
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// The compact chain of adjoint.hip and ragged.hip: NP/32 waves; wave w owns outputs
+// o = 32w + (lane & 31), the two half-waves split the inputs (lane >> 5 = input half h).
+template <int NP>
+struct ChainGeo {
+  static constexpr int NW = NP / 32;     // waves
+  static constexpr int NT = NW * kWave;  // threads
+  static constexpr int HALF = NP / 2;    // inputs per lane
+  static constexpr int XS = HALF + 4;    // LDS stride of an input half (the two half-wave
+                                         // broadcast addresses fall in different banks)
+  static constexpr int PD = 8;           // steps of loads in flight
+  static constexpr int K = NP / 64;      // states per lane of a one-wave row pass
+};
 
 }  // namespace hmm355

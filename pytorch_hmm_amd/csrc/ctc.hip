@@ -85,23 +85,6 @@ struct CtcShared {
   int wpos[2];
 };
 
-__device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ void ctc_global_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __threadfence_block();
-  __syncthreads();
-}
-
-// log(e^a + e^b + e^c); -inf when all three are
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(a, b), c);
-  const float ms = m == -INFINITY ? 0.f : m;
-  const float s = expf(a - ms) + expf(b - ms) + expf(c - ms);
-  const float r = ms + logf(s);
-  return m == -INFINITY ? -INFINITY : r;
-}
-
 template <int P, int NT, bool VIT>
 __device__ __forceinline__ void ctc_run(const CtcArgs& a, const int job, CtcShared& sh) {
   constexpr int AH = kCtcAhead;
@@ -266,7 +249,7 @@ __device__ __forceinline__ void ctc_run(const CtcArgs& a, const int job, CtcShar
     sh.wpos[0] = Tb - 1;
     sh.wpos[1] = a2 > a1 ? Sb - 2 : Sb - 1;
   }
-  ctc_global_barrier();  // every thread's choices are in memory
+  global_barrier();  // every thread's choices are in memory
   for (;;) {
     __syncthreads();
     int t = sh.wpos[0], s = sh.wpos[1];
@@ -359,7 +342,7 @@ __global__ void __launch_bounds__(kCtcThreads) ctc_grad_kernel(CtcGradArgs a) {
   __syncthreads();
   for (int i = k; i < Lb; i += NT)
     if (nxt[i] >= 0) has_prev[nxt[i]] = 1;
-  ctc_global_barrier();  // the zeros are in memory before any sum is stored over them
+  global_barrier();  // the zeros are in memory before any sum is stored over them
 
   const int lane = k & 63, w = k >> 6;
   for (int t = t0 + w; t < tend; t += NT / 64) {

@@ -85,12 +85,6 @@ size_t dc_lds_bytes(int G, int S, int R, bool lt_lds) {
   return n < kDcMinLds ? kDcMinLds : n;
 }
 
-__device__ __forceinline__ void dc_memory_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __threadfence_block();
-  __syncthreads();
-}
-
 // SPLIT (1 or kDcSplit, the latter with R = 1 only): lanes per cell.  Lane l of a wave has cell
 // l % (64 / SPLIT) of the wave's 64 / SPLIT cells and the part l / (64 / SPLIT) of the range of p,
 // consecutive p per part, so the parts combine in ascending order of p.
@@ -290,7 +284,7 @@ __global__ void __launch_bounds__(kDcMaxThreads) dchmm_kernel(DcArgs a) {
     }
   }
   if (T == 1) return;
-  dc_memory_barrier();  // every thread's psi bytes are in memory, and the rows in LDS are dead
+  global_barrier();  // every thread's psi bytes are in memory, and the rows in LDS are dead
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (tid + j * NT < Gk) wstate[tid + j * NT] = endstate[j];

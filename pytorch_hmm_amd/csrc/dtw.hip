@@ -39,19 +39,6 @@ constexpr int kWalkBlocks = 128;                     // ... and column blocks (b
 
 constexpr int kModeSym = 0, kModeRJ = 1, kModeSoft = 2;
 
-__device__ __forceinline__ int clamp_len(const int* len, size_t b, int full) {
-  if (!len) return full;
-  const int v = len[b];
-  return v < 1 ? 1 : (v > full ? full : v);
-}
-
-// workgroup barrier after which every thread sees the global stores made before it
-__device__ __forceinline__ void global_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __threadfence_block();
-  __syncthreads();
-}
-
 __device__ __forceinline__ float& comp(float4& v, int x) { return reinterpret_cast<float*>(&v)[x]; }
 
 // softmin_g(a, b, c) = m - g log sum exp(-(c - m) / g), +inf when every candidate is
@@ -102,7 +89,7 @@ __global__ void __launch_bounds__(kDtwThreads) dtw_fwd_kernel(DtwArgs a) {
   const int k = threadIdx.x;
   const size_t b = blockIdx.x;
   const int N = a.N, M = a.M;
-  const int n = clamp_len(a.n_len, b, N), m = clamp_len(a.m_len, b, M);
+  const int n = seq_len(a.n_len, b, N), m = seq_len(a.m_len, b, M);
   const int Q = (M + 3) >> 2, Qm = (m + 3) >> 2;
   const float* D = a.dist + b * (size_t)N * M;
   const size_t RS = (size_t)M + 1;  // row stride of R
@@ -370,7 +357,7 @@ __global__ void __launch_bounds__(kDtwThreads) softdtw_grad_kernel(GradArgs a) {
   const int k = threadIdx.x;
   const size_t b = blockIdx.x;
   const int N = a.N, M = a.M;
-  const int n = clamp_len(a.n_len, b, N), m = clamp_len(a.m_len, b, M);
+  const int n = seq_len(a.n_len, b, N), m = seq_len(a.m_len, b, M);
   const int Qm = (m + 3) >> 2;
   const size_t RS = (size_t)M + 1;
   const float* Rm = a.R + b * ((size_t)N + 1) * RS;

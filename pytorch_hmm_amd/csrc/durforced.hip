@@ -101,79 +101,6 @@ struct DfArgs {
   int jobs[3];
 };
 
-__device__ __forceinline__ int df_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// this workgroup's global stores are visible to all of its threads
-__device__ __forceinline__ void df_global_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __threadfence_block();
-  __syncthreads();
-}
-
-// All-reduce over the `sub` lanes of a position (a power of two, aligned inside a wave): quad_perm
-// [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror, then the row pairs and the wave halves.
-// A lane and its partner combine the same two numbers, so every lane of the group ends with the
-// same bits.  (`sub` is uniform: the branches are scalar.)
-__device__ __forceinline__ float df_grp_max(float v, int sub) {
-  if (sub >= 2) v = fmaxf(v, dpp_f<0xB1>(v));
-  if (sub >= 4) v = fmaxf(v, dpp_f<0x4E>(v));
-  if (sub >= 8) v = fmaxf(v, dpp_f<0x141>(v));
-  if (sub >= 16) v = fmaxf(v, dpp_f<0x140>(v));
-  if (sub >= 32) {
-    float a = v, b = v;
-    permlane16_swap(a, b);
-    v = fmaxf(a, b);
-  }
-  if (sub >= 64) {
-    float a = v, b = v;
-    permlane32_swap(a, b);
-    v = fmaxf(a, b);
-  }
-  return v;
-}
-__device__ __forceinline__ float df_grp_sum(float v, int sub) {
-  if (sub >= 2) v += dpp_f<0xB1>(v);
-  if (sub >= 4) v += dpp_f<0x4E>(v);
-  if (sub >= 8) v += dpp_f<0x141>(v);
-  if (sub >= 16) v += dpp_f<0x140>(v);
-  if (sub >= 32) {
-    float a = v, b = v;
-    permlane16_swap(a, b);
-    v = a + b;
-  }
-  if (sub >= 64) {
-    float a = v, b = v;
-    permlane32_swap(a, b);
-    v = a + b;
-  }
-  return v;
-}
-// (value, d - 1): the larger value, of equal values the smaller d
-__device__ __forceinline__ void df_grp_argmax(float& v, int& i, int sub) {
-  if (sub >= 2) argmax_combine(v, i, dpp_f<0xB1>(v), dpp_i<0xB1>(i));
-  if (sub >= 4) argmax_combine(v, i, dpp_f<0x4E>(v), dpp_i<0x4E>(i));
-  if (sub >= 8) argmax_combine(v, i, dpp_f<0x141>(v), dpp_i<0x141>(i));
-  if (sub >= 16) argmax_combine(v, i, dpp_f<0x140>(v), dpp_i<0x140>(i));
-  if (sub >= 32) {
-    float a = v, b = v;
-    int ia = i, ib = i;
-    permlane16_swap(a, b);
-    permlane16_swap_i(ia, ib);
-    argmax_combine(a, ia, b, ib);
-    v = a;
-    i = ia;
-  }
-  if (sub >= 64) {
-    float a = v, b = v;
-    int ia = i, ib = i;
-    permlane32_swap(a, b);
-    permlane32_swap_i(ia, ib);
-    argmax_combine(a, ia, b, ib);
-    v = a;
-    i = ia;
-  }
-}
-
 // Row stride of the ring and of dur_lp in LDS: the smallest DS >= Dmax that is an odd multiple of
 // `sub`.  The 32 lanes of a half wave are 32 / sub positions times sub consecutive slots; their rows
 // then start sub banks apart and the half wave's 32 words sit in 32 different banks (with the
@@ -211,8 +138,8 @@ __device__ __forceinline__ void df_chain_run(const DfArgs& a, const int job, flo
   const int lane = tid & 63, wave = tid >> 6;
   const int T = a.T, C = a.C, Lm = a.Lm, Dm = a.Dm, SUB = a.SUB, NT = a.NT, DS = a.DS;
   const int NW = NT >> 6;
-  const int Tb = df_clamp(a.in_len[b], 1, T);
-  const int Lb = df_clamp(a.st_len[b], 1, Lm);
+  const int Tb = clamp_int(a.in_len[b], 1, T);
+  const int Lb = clamp_int(a.st_len[b], 1, Lm);
   const bool back = job == kJobBackward;
   const int p = tid / SUB, sub = tid & (SUB - 1);  // p: the position in the job's own order
   const bool live = p < Lb;
@@ -274,7 +201,7 @@ __device__ __forceinline__ void df_chain_run(const DfArgs& a, const int job, flo
   }
   if (keep)
     for (int t = Tb + tid; t < T; t += NT) Mj[t] = 0.f;
-  df_global_barrier();
+  global_barrier();
 
   const int myc = live ? cls[l] : -1;
   float* vrow = vals + l * DS;
@@ -368,11 +295,11 @@ __device__ __forceinline__ void df_chain_run(const DfArgs& a, const int job, flo
     }
     float Fv;
     if (VIT) {
-      df_grp_argmax(mx, bd, SUB);
+      grp_argmax_rt(mx, bd, SUB);
       Fv = mx;
       if (lead) bp[(size_t)t * Lm + l] = (unsigned char)bd;
     } else {
-      mx = df_grp_max(mx, SUB);
+      mx = grp_max_rt(mx, SUB);
       const float ms = mx == NINF ? 0.f : mx;
       float sum = 0.f;
       if (live) {
@@ -392,7 +319,7 @@ __device__ __forceinline__ void df_chain_run(const DfArgs& a, const int job, flo
         }
         for (int k = k0; k < Dm; k += SUB) sum += expf(vrow[k] + drow[dur_of(k)] - ms);
       }
-      sum = df_grp_sum(sum, SUB);
+      sum = grp_sum_rt(sum, SUB);
       Fv = mx == NINF ? NINF : ms + logf(sum);
     }
     if (lead) {
@@ -440,7 +367,7 @@ __device__ __forceinline__ void df_chain_run(const DfArgs& a, const int job, flo
     wpos[0] = Tb - 1;
     wpos[1] = Lb - 1;
   }
-  df_global_barrier();  // every lead's choices and the zeroed durations are in memory
+  global_barrier();  // every lead's choices and the zeroed durations are in memory
   for (;;) {
     __syncthreads();
     int t = wpos[0], q = wpos[1];
@@ -509,8 +436,8 @@ struct DfGradArgs {
 // -inf frames: O(a..t,l) = P_t - P_a-1 when the counts agree, else -inf
 __device__ void df_prefix_run(const DfGradArgs& a, int b) {
   const int l = threadIdx.x, T = a.T, Lm = a.Lm, C = a.C;
-  const int Tb = df_clamp(a.in_len[b], 1, T);
-  const int Lb = df_clamp(a.st_len[b], 1, Lm);
+  const int Tb = clamp_int(a.in_len[b], 1, T);
+  const int Lb = clamp_int(a.st_len[b], 1, Lm);
   if (l >= Lb) return;
   const int c = a.ids ? a.ids[(size_t)b * Lm + l] : l;
   const bool ok = c >= 0 && c < C;
@@ -542,8 +469,8 @@ __global__ void __launch_bounds__(64 * kDfGammaChunks) durforced_gamma_kernel(Df
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b = blockIdx.x / a.gx, T = a.T, Lm = a.Lm;
   const float NINF = -INFINITY;
-  const int Tb = df_clamp(a.in_len[b], 1, T);
-  const int Lb = df_clamp(a.st_len[b], 1, Lm);
+  const int Tb = clamp_int(a.in_len[b], 1, T);
+  const int Lb = clamp_int(a.st_len[b], 1, Lm);
   const float llf = a.lls[b];
   const bool feasible = llf > NINF;
   const double ll = feasible ? (double)llf : 0.0;
@@ -597,8 +524,8 @@ __global__ void __launch_bounds__(256) durforced_count_kernel(DfGradArgs a) {
   if (idx >= cells) return;
   const float NINF = -INFINITY;
   const int l = idx % Lm, d = idx / Lm;  // duration d + 1
-  const int Tb = df_clamp(a.in_len[b], 1, T);
-  const int Lb = df_clamp(a.st_len[b], 1, Lm);
+  const int Tb = clamp_int(a.in_len[b], 1, T);
+  const int Lb = clamp_int(a.st_len[b], 1, Lm);
   const float llf = a.lls[b];
   const float du = a.dur[((size_t)b * Lm + l) * Dm + d];
   const int TC = (Tb + a.chunks - 1) / a.chunks;
@@ -645,8 +572,8 @@ __global__ void __launch_bounds__(256) durforced_reduce_kernel(DfGradArgs a) {
   const int t0 = (blk % a.tiles) * kDfClassRows;
   const int t1 = t0 + kDfClassRows < T ? t0 + kDfClassRows : T;
   const int lane = k & 63, w = k >> 6;
-  const int Tb = df_clamp(a.in_len[b], 1, T);
-  const int Lb = df_clamp(a.st_len[b], 1, Lm);
+  const int Tb = clamp_int(a.in_len[b], 1, T);
+  const int Lb = clamp_int(a.st_len[b], 1, Lm);
   // this workgroup's frames start as zero: classes that are not in the chain, frames >= T_b, an
   // infeasible pair
   float* g0 = a.grad + ((size_t)b * T + t0) * C;
@@ -668,7 +595,7 @@ __global__ void __launch_bounds__(256) durforced_reduce_kernel(DfGradArgs a) {
   __syncthreads();
   for (int i = k; i < Lb; i += 256)
     if (nxt[i] >= 0) has_prev[nxt[i]] = 1;
-  df_global_barrier();  // the zeros are in memory before any sum is stored over them
+  global_barrier();  // the zeros are in memory before any sum is stored over them
   for (int t = t0 + w; t < tend; t += 4) {
     const float* gm = a.gamma + ((size_t)b * T + t) * Lm;
     float* gr = a.grad + ((size_t)b * T + t) * C;

@@ -35,22 +35,9 @@ template <int NP>
 hipError_t launch_fb(const RecArgs& fa, const RecArgs& fb, const PostArgs& pa, bool prep, hipStream_t st, int nfollow);
 template <int NP>
 hipError_t launch_fb_pair(const PairArgs& pa, int B, hipStream_t st);
-// OBS_LOG: the row maxima M_t = max_j lo_t[j] (one wave per (b,t) row, grid-stride); the
-// chains stage e_t = exp(lo_t - M_t) and add M_t to the log-scales (recur.h rec_stage /
-// rec_flush), so log-emissions far below -87 (Gaussian log-densities at D = 80) do not
-// underflow.  A row without a finite maximum gets M = 0 (its emissions stay exp(lo)).
-__global__ void __launch_bounds__(256) row_max_kernel(const float* __restrict__ lo, int N, size_t rows,
-                                                      float* __restrict__ m) {
-  const int l = threadIdx.x & 63;
-  const size_t nw = ((size_t)gridDim.x * blockDim.x) >> 6;
-  for (size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < rows; row += nw) {
-    const float* src = lo + row * N;
-    float v = -INFINITY;
-    for (int j = l; j < N; j += 64) v = fmaxf(v, src[j]);
-    v = wave_max_dpp2(v);
-    if (l == 0) m[row] = (v > -INFINITY && v < INFINITY) ? v : 0.f;
-  }
-}
+// OBS_LOG: the row maxima M_t = max_j lo_t[j] (common.h row_max_kernel); the chains stage
+// e_t = exp(lo_t - M_t) and add M_t to the log-scales (recur.h rec_stage / rec_flush), so
+// log-emissions far below -87 (Gaussian log-densities at D = 80) do not underflow.
 
 // Workspace layout (documented in include/hmm355.h for adjoint callers):
 //   U (B,T,NP) | V (B,T,NP) | LA (B,T) | LB (B,T) | BandDesc | beta init (B,NP) | its scale (B)
@@ -165,7 +152,8 @@ HMM355_API int hmm355_forward_backward_plan_f32(const float* obs, int obs_mode, 
   const float* rmax = nullptr;
   if (obs_mode == HMM355_OBS_LOG) {
     const size_t rows = (size_t)B * T;
-    HMM355_TRY(launch(row_max_kernel, dim3(row_grid(rows, 4096)), dim3(256), 0, st, obs, N, rows, w.rmax));
+    HMM355_TRY(launch(row_max_kernel<false>, dim3(row_grid(rows, 4096)), dim3(256), 0, st, obs, nullptr, T, N, rows,
+                      w.rmax));
     rmax = w.rmax;
   }
   RecArgs fa{obs, log_P, log_p0, w.U, w.LA, loglik, B, T, N, obs_mode, NP, band, nullptr, nullptr, nullptr, rmax, nullptr};

@@ -101,30 +101,6 @@ struct ForcedShared {
   int wpos[2];
 };
 
-__device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ void forced_global_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __threadfence_block();
-  __syncthreads();
-}
-
-// log(e^a + e^b + e^c); -inf when all three are
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(a, b), c);
-  const float ms = m == -INFINITY ? 0.f : m;
-  const float s = expf(a - ms) + expf(b - ms) + expf(c - ms);
-  const float r = ms + logf(s);
-  return m == -INFINITY ? -INFINITY : r;
-}
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float ms = m == -INFINITY ? 0.f : m;
-  const float s = expf(a - ms) + expf(b - ms);
-  const float r = ms + logf(s);
-  return m == -INFINITY ? -INFINITY : r;
-}
-
 template <int P, int NT, bool VIT, bool PLAIN>
 __device__ __forceinline__ void forced_run(const ForcedArgs& a, const int job, ForcedShared& sh) {
   constexpr int AH = kForcedAhead;
@@ -310,7 +286,7 @@ __device__ __forceinline__ void forced_run(const ForcedArgs& a, const int job, F
     sh.wpos[0] = Tb - 1;
     sh.wpos[1] = Sb - 1;
   }
-  forced_global_barrier();  // every thread's choices and the zeroed durations are in memory
+  global_barrier();  // every thread's choices and the zeroed durations are in memory
   int last = -1, run = 0;   // lane 0: the position of the frames walked last and how many they are
   for (;;) {
     __syncthreads();
@@ -445,7 +421,7 @@ __global__ void __launch_bounds__(kForcedThreads) forced_grad_kernel(ForcedGradA
     for (int i = k; i < Sb; i += NT)
       if (nxt[i] >= 0) has_prev[nxt[i]] = 1;
   }
-  forced_global_barrier();  // the zeros are in memory before any sum is stored over them
+  global_barrier();  // the zeros are in memory before any sum is stored over them
 
   for (int t = t0 + w; t < tend; t += NW) {
     const float* ar = al + (size_t)t * Sm;

@@ -98,33 +98,6 @@ struct HsLds {
 };
 
 constexpr int kHsOOB = 0x7FFFFFF0;  // a buffer offset past every record count: the store is dropped
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t hs_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-// all-reduce over the SUB lanes of a state group (16: one DPP row; 8: half a row; 4: a quad)
-template <int SUB>
-__device__ __forceinline__ float grp_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));                       // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_f<0x4E>(v));                       // quad_perm [2,3,0,1]
-  if constexpr (SUB == 8) v = fmaxf(v, dpp_f<0x141>(v));   // row_half_mirror
-  if constexpr (SUB == 16) {
-    v = fmaxf(v, dpp_f<0x124>(v));                    // row_ror:4
-    v = fmaxf(v, dpp_f<0x128>(v));                    // row_ror:8
-  }
-  return v;
-}
-template <int SUB>
-__device__ __forceinline__ int grp_min_i(int v) {
-  v = min(v, dpp_i<0xB1>(v));
-  v = min(v, dpp_i<0x4E>(v));
-  if constexpr (SUB == 8) v = min(v, dpp_i<0x141>(v));
-  if constexpr (SUB == 16) {
-    v = min(v, dpp_i<0x124>(v));
-    v = min(v, dpp_i<0x128>(v));
-  }
-  return v;
-}
 
 template <int SUB, int NJ, int SMAX>
 __global__ void __launch_bounds__((HsG<SUB, NJ, SMAX>::NT)) hsmm_fwd_kernel(HsArgs a) {
@@ -139,8 +112,8 @@ __global__ void __launch_bounds__((HsG<SUB, NJ, SMAX>::NT)) hsmm_fwd_kernel(HsAr
   const int q = (s % SUB) * NPRED + s / SUB;
   const float* lp = a.lp + (size_t)b * T * S;
   // Dm / M rows: one lane per state stores (buffer offsets past the records drop the rest)
-  const __amdgpu_buffer_rsrc_t dg_r = hs_rsrc(a.Dg + (size_t)b * T * S, (unsigned)T * S * 4u);
-  const __amdgpu_buffer_rsrc_t mg_r = hs_rsrc(a.Mg + (size_t)b * T * S, (unsigned)T * S * 4u);
+  const __amdgpu_buffer_rsrc_t dg_r = make_rsrc(a.Dg + (size_t)b * T * S, (unsigned)T * S * 4u);
+  const __amdgpu_buffer_rsrc_t mg_r = make_rsrc(a.Mg + (size_t)b * T * S, (unsigned)T * S * 4u);
   const int st_off = (live && sub == 0) ? s * 4 : kHsOOB;
 
   auto dur_at = [&](int r, int age) -> float {  // -inf beyond Dmax and for padding states

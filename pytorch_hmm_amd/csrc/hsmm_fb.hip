@@ -88,36 +88,6 @@ struct HfArgs {
   int jobs[3];
 };
 
-// All-reduce over the `sub` lanes that share a state (a power of two, aligned inside a wave), on
-// DPP and permlane swaps: quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror, then
-// the row pairs and the wave halves.  Every level pairs a lane with the lane that holds the other
-// half's value, so a lane and its partner add the same two numbers: the sum has the same bits in
-// every lane of the group.  (`sub` is uniform: the branches are scalar.)
-template <typename Op>
-__device__ __forceinline__ float grp_reduce(float v, int sub, Op op) {
-  if (sub >= 2) v = op(v, dpp_f<0xB1>(v));
-  if (sub >= 4) v = op(v, dpp_f<0x4E>(v));
-  if (sub >= 8) v = op(v, dpp_f<0x141>(v));
-  if (sub >= 16) v = op(v, dpp_f<0x140>(v));
-  if (sub >= 32) {
-    float a = v, b = v;
-    permlane16_swap(a, b);  // a = rows [0,0,2,2], b = rows [1,1,3,3]
-    v = op(a, b);
-  }
-  if (sub >= 64) {
-    float a = v, b = v;
-    permlane32_swap(a, b);
-    v = op(a, b);
-  }
-  return v;
-}
-__device__ __forceinline__ float grp_max_rt(float v, int sub) {
-  return grp_reduce(v, sub, [](float a, float b) { return fmaxf(a, b); });
-}
-__device__ __forceinline__ float grp_sum_rt(float v, int sub) {
-  return grp_reduce(v, sub, [](float a, float b) { return a + b; });
-}
-
 __global__ void __launch_bounds__(256) hsmm_fb_prep_kernel(HfArgs a, int row_blocks) {
   const int tid = threadIdx.x;
   const float NINF = -INFINITY;

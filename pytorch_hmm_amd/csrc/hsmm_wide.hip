@@ -82,11 +82,6 @@ __global__ void __launch_bounds__(256) hsmm_wide_osum_kernel(HwArgs a) {
   }
 }
 
-// an L1-bypassing load (agent scope): M rows written earlier by other waves of this workgroup
-__device__ __forceinline__ float ld_fresh(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // delta(end e, state s, duration d) from M (oracle DELTA_AT)
 __device__ __forceinline__ float hw_delta(const HwArgs& a, int b, int e, int s, int d) {
   const int st = e - d + 1;
@@ -96,28 +91,6 @@ __device__ __forceinline__ float hw_delta(const HwArgs& a, int b, int e, int s, 
   if (st == 0) return o + u;
   const float m = ld_fresh(a.Mh + ((size_t)b * a.T + st) * a.S + s);
   return m == -INFINITY ? -INFINITY : (m + o) + u;
-}
-
-// workgroup reductions over kHwNT threads (16 waves): max of a float; min of an int
-__device__ __forceinline__ float wg_max(float v, float* red) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int k = 1; k < kHwNT / 64; ++k) r = fmaxf(r, red[k]);
-  return r;
-}
-__device__ __forceinline__ int wg_min(int v, int* red) {
-  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  int r = red[0];
-  for (int k = 1; k < kHwNT / 64; ++k) r = min(r, red[k]);
-  return r;
 }
 
 __global__ void __launch_bounds__(kHwNT) hsmm_wide_kernel(HwArgs a) {
@@ -189,11 +162,11 @@ __global__ void __launch_bounds__(kHwNT) hsmm_wide_kernel(HwArgs a) {
   const int nk = S * Dm;
   float bv = -INFINITY;
   for (int j = tid; j < nk; j += kHwNT) bv = fmaxf(bv, hw_delta(a, b, T - 1, j % S, j / S + 1));
-  const float best = wg_max(bv, redf);
+  const float best = wg_max<kHwNT>(bv, redf);
   int bk = 0x7fffffff;
   for (int j = tid; j < nk; j += kHwNT)
     if (hw_delta(a, b, T - 1, j % S, j / S + 1) == best) bk = min(bk, (j % S) * Dm + j / S);
-  bk = wg_min(bk, redi);
+  bk = wg_min<kHwNT>(bk, redi);
   if (bk == 0x7fffffff) bk = 0;  // every score -inf: (s, d) = (0, 1) as the reference's init
   if (tid == 0) a.scores[b] = best;
 
@@ -224,7 +197,7 @@ __global__ void __launch_bounds__(kHwNT) hsmm_wide_kernel(HwArgs a) {
         const float x = (sp == cs || pv == -INFINITY) ? -INFINITY : pv + lT[(size_t)sp * S];
         if (x != -INFINITY && (x + od) + ud == F) win = min(win, sp * Dm + dp - 1);
       }
-      win = wg_min(win, redi);
+      win = wg_min<kHwNT>(win, redi);
       if (win == 0x7fffffff) win = 0;  // (unreachable: the candidate attaining M qualifies)
       ns = win / Dm;
       nd = win % Dm + 1;

@@ -74,4 +74,9 @@ HMM355_HD float logcr_fast(float s, const double* __restrict__ tab) {
   return special ? sv : v;
 }
 
+#ifdef __HIPCC__
+// the table in device memory
+__device__ const double g_logcr_tab[256] = {HMM355_LOGCR_TABLE};
+#endif
+
 }  // namespace hmm355

@@ -45,8 +45,6 @@
 namespace hmm355 {
 namespace {
 
-__device__ const double nb_logcr_tab[256] = {HMM355_LOGCR_TABLE};
-
 // source parts per destination state: quarters, halves at NP = 256 (a quarter there would mean
 // 1024 threads with 128 VGPRs each, which the column part and the list do not fit)
 template <int NP>
@@ -156,7 +154,7 @@ __global__ void __launch_bounds__(kNbSlices<NP> * NP) nbest_kernel(NbArgs a) {
   }
   const size_t rb = (size_t)b * T;
   auto load = [&](int q) { return a.obs[(rb + (q < len ? q : len - 1)) * N + jc]; };
-  auto stage = [&](float x) { return a.prob ? logcr_fast(x + 1e-8f, nb_logcr_tab) : x; };
+  auto stage = [&](float x) { return a.prob ? logcr_fast(x + 1e-8f, g_logcr_tab) : x; };
   // part g >= 1 stages the steps q with q % D + 1 == g: its first one is g - 1, or D for g = 1
   float rx = 0.f;
   if (s > 0) rx = load(s == 1 ? G::D : s - 1);

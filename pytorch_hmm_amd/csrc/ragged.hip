@@ -47,21 +47,10 @@
 namespace hmm355 {
 namespace {
 
-__device__ const double rag_logcr_tab[256] = {HMM355_LOGCR_TABLE};
-
-template <int NP>
-struct RagGeo {
-  static constexpr int NW = NP / 32;     // waves
-  static constexpr int NT = NW * kWave;  // threads
-  static constexpr int HALF = NP / 2;    // inputs per lane
-  static constexpr int XS = HALF + 4;    // LDS stride of an input half (the two half-wave
-                                         // broadcast addresses fall in different banks)
-  static constexpr int PD = 8;           // steps of loads in flight
-  static constexpr int K = NP / 64;      // states per lane of a one-wave row pass
-};
-
 constexpr int kRagChunk = 64;  // psi rows per backtrace chunk
 
+// the sequence's length clamped to 1 .. T (common.h seq_len less its test for null lengths, which
+// the entry points refuse; with the test these kernels compile to other code)
 __device__ __forceinline__ int rag_len(const int* lengths, int b, int T) {
   const int n = lengths[b];
   return n < 1 ? 1 : (n > T ? T : n);
@@ -84,7 +73,8 @@ struct RagFbArgs {
 };
 
 // OBS_LOG: M_t = max_j lo_t[j] of the valid frames (0 for a row without a finite maximum and in
-// padded frames, which are not read).  One wave per row, grid-stride.
+// padded frames, which are not read).  One wave per row, grid-stride.  (common.h's
+// row_max_kernel<true> less the test for null lengths.)
 __global__ void __launch_bounds__(256) rag_row_max_kernel(const float* __restrict__ lo, const int* __restrict__ lengths,
                                                           int T, int N, size_t rows, float* __restrict__ m) {
   const int l = threadIdx.x & 63;
@@ -104,7 +94,7 @@ __global__ void __launch_bounds__(256) rag_row_max_kernel(const float* __restric
 // CH 0: alpha chain (time ascending), CH 1: beta chain (time descending from len - 1)
 template <int NP, int OBS, int CH>
 __device__ __forceinline__ void rag_fb_chain(const RagFbArgs& a, int b, float* lds) {
-  using G = RagGeo<NP>;
+  using G = ChainGeo<NP>;
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   const int o = 32 * w + (l & 31), h = l >> 5;
   const int T = a.T, N = a.N;
@@ -232,8 +222,8 @@ __device__ __forceinline__ void rag_fb_chain(const RagFbArgs& a, int b, float* l
 }
 
 template <int NP, int OBS>
-__global__ void __launch_bounds__(RagGeo<NP>::NT) rag_fb_kernel(RagFbArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * RagGeo<NP>::XS];
+__global__ void __launch_bounds__(ChainGeo<NP>::NT) rag_fb_kernel(RagFbArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * ChainGeo<NP>::XS];
   const int b = blockIdx.x >> 1;
   if (blockIdx.x & 1) rag_fb_chain<NP, OBS, 1>(a, b, lds);
   else rag_fb_chain<NP, OBS, 0>(a, b, lds);
@@ -420,8 +410,8 @@ struct RagVitArgs {
 };
 
 template <int NP, int OBS>
-__global__ void __launch_bounds__(RagGeo<NP>::NT) rag_vit_kernel(RagVitArgs a) {
-  using G = RagGeo<NP>;
+__global__ void __launch_bounds__(ChainGeo<NP>::NT) rag_vit_kernel(RagVitArgs a) {
+  using G = ChainGeo<NP>;
   __shared__ __attribute__((aligned(16))) float xb[2 * 2 * G::XS];
   __shared__ __attribute__((aligned(16))) uint8_t ps[kRagChunk][NP];
   __shared__ int st[kRagChunk];
@@ -448,7 +438,7 @@ __global__ void __launch_bounds__(RagGeo<NP>::NT) rag_vit_kernel(RagVitArgs a) {
     const int qq = q < len ? q : len - 1;
     rx[p] = a.obs[(rb + qq) * N + oc];
   };
-  auto stage = [&](int p) { return OBS == HMM355_OBS_PROB ? logcr_fast(rx[p] + 1e-8f, rag_logcr_tab) : rx[p]; };
+  auto stage = [&](int p) { return OBS == HMM355_OBS_PROB ? logcr_fast(rx[p] + 1e-8f, g_logcr_tab) : rx[p]; };
 #pragma unroll
   for (int p = 0; p < G::PD; ++p) load(p, p);
   float e = stage(0);
@@ -605,7 +595,7 @@ HMM355_API int hmm355_viterbi_ragged_f32(const float* obs, int obs_mode, const f
   return with_np(NP, [&](auto np) {
     return with_flag(prob, [&](auto p) {
       constexpr int OBS = p() ? HMM355_OBS_PROB : HMM355_OBS_LOG;
-      return launch(rag_vit_kernel<np(), OBS>, dim3(B), dim3(RagGeo<np()>::NT), 0, st, a);
+      return launch(rag_vit_kernel<np(), OBS>, dim3(B), dim3(ChainGeo<np()>::NT), 0, st, a);
     });
   });
 }
@@ -645,7 +635,7 @@ HMM355_API int hmm355_forward_backward_ragged_f32(const float* obs, int obs_mode
   HMM355_TRY(with_np(NP, [&](auto np) {
     return with_flag(prob, [&](auto p) {
       constexpr int OBS = p() ? HMM355_OBS_PROB : HMM355_OBS_LOG;
-      return launch(rag_fb_kernel<np(), OBS>, dim3(2 * B), dim3(RagGeo<np()>::NT), 0, st, fa);
+      return launch(rag_fb_kernel<np(), OBS>, dim3(2 * B), dim3(ChainGeo<np()>::NT), 0, st, fa);
     });
   }));
   RagPostArgs pa{w.U, w.V, w.LA, w.LB, w.CA, w.CB, w.rmax, w.bscale, lengths,

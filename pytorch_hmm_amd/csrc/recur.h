@@ -59,12 +59,6 @@ typedef unsigned int u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned 
 constexpr int emis_ahead(int kind) {
   return kind == kFbAlpha ? HMM355_EMIS_AHEAD_ALPHA : kind == kFbBeta ? HMM355_EMIS_AHEAD_BETA : HMM355_EMIS_AHEAD_VIT;
 }
-// HMM355_BLOCK_EDGE: 0 builds rec_band's chains with the block loop of round 11 (diagnostic
-// builds: the parent's figures from this tree, tools/band_stamps.py)
-#ifndef HMM355_BLOCK_EDGE
-#define HMM355_BLOCK_EDGE 1
-#endif
-constexpr bool kBlockEdge = HMM355_BLOCK_EDGE;
 // The form of the step's wave reduction (wave_red_level) by chain: what measured faster per chain
 // (DESIGN section 14 round 11): beta and Viterbi both triples, alpha, whose reduction is not
 // filled, the first one.  HMM355_RED_FORM (common.h) sets all three, for diagnostic builds.
@@ -577,9 +571,8 @@ __device__ __forceinline__ int rec_tau(int q, int T) {
   return KIND == kFbBeta ? T - 1 - q : q;
 }
 
-// the log table of logcr.h; each wave that stages Viterbi emissions copies it into LDS itself
-// (identical values from every copier, so no barrier: a wave's own LDS writes precede its reads)
-__device__ const double g_logcr_tab[256] = {HMM355_LOGCR_TABLE};
+// the log table (logcr.h g_logcr_tab): each wave that stages Viterbi emissions copies it into LDS
+// itself (identical values from every copier, so no barrier: a wave's own LDS writes precede its reads)
 template <int NP>
 __device__ __forceinline__ void rec_logt_fill(float* lds, int l) {
   double* t = reinterpret_cast<double*>(lds + RC<NP>::OFF_LOGT);
@@ -1368,7 +1361,8 @@ constexpr int win_shift_term(int m, int NB, int NWIN, int TD0) {
 // 16-step block and one after the last row, matching the helpers' barriers.  `lds` is the
 // chain's own RC<NP> layout.
 // EDGE: the loop over whole blocks of round 12 (run_edge below), whose barrier stands EA steps
-// before the block's end; rec_band's chains take it, the pair kernel's keep the loop they had.
+// before the block's end; rec_band's chains take it, the pair kernel's (fbpair.h: EA = 1, two
+// layouts in a workgroup) keep run_blocks, the loop they had.
 template <int NP, int KIND, int WP, int TD0 = 0, int TW = 0, int EA = emis_ahead(KIND), bool EDGE = false>
 __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, const BandDesc* __restrict__ d) {
   using C = RC<NP>;
@@ -1734,7 +1728,8 @@ __device__ __forceinline__ void band_chain(const RecArgs& a, float* lds, int b, 
     }
   };
   // The same blocks with a hot loop that holds only whole ones (EDGE).
-  // Block 0 (no step 0) and a partial last block run rolled, as above.  The whole blocks 1 ..
+  // Block 0 (no step 0) and a partial last block run rolled: one step at a time, each storing its
+  // normaliser word as it is computed, the block barrier behind the last.  The whole blocks 1 ..
   // T / 16 - 1 run in a loop that tests its trip count and nothing else:
   //  - its bases (emission slot, the next block's, row-ring slot, the wrapped row, the normaliser
   //    word) advance by an add and a wrap each; no % 3, no multiply, no q0 / q1;
@@ -1934,7 +1929,7 @@ __device__ __forceinline__ void rec_band(const RecArgs& a, float* lds, int b, co
   lds_barrier();
 
   if (w == 0) {
-    band_chain<NP, KIND, WP, TD0, TW, emis_ahead(KIND), kBlockEdge>(a, lds, b, d);
+    band_chain<NP, KIND, WP, TD0, TW, emis_ahead(KIND), true>(a, lds, b, d);
     return;
   }
   // ---------------------------------------------------------------- helper waves

@@ -76,19 +76,6 @@ struct SmLds {
   float dmx[2][kSmS];            // Dm / A of the current end time (double-buffered)
 };
 
-__device__ __forceinline__ float sm_row_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x124>(v));
-  return fmaxf(v, dpp_f<0x128>(v));
-}
-__device__ __forceinline__ int sm_row_min_i(int v) {
-  v = min(v, dpp_i<0xB1>(v));
-  v = min(v, dpp_i<0x4E>(v));
-  v = min(v, dpp_i<0x124>(v));
-  return min(v, dpp_i<0x128>(v));
-}
-
 __device__ __forceinline__ float sm_seg_obs(float cs, float Q, bool gaussian) {
   return gaussian ? cs - 0.5f * Q : Q;
 }
@@ -200,7 +187,7 @@ __global__ void __launch_bounds__(kSmThreads) smk_fwd_kernel(SmArgs a) {
       }
       mx = fmaxf(mx, v[j]);
     }
-    mx = sm_row_max(mx);
+    mx = grp_max<kSmSub>(mx);
     float red = mx;  // Viterbi: Dm[t][s]; forward: A[t][s] = LSE_d
     if constexpr (!kViterbi) {
       float se = 0.f;
@@ -225,7 +212,7 @@ __global__ void __launch_bounds__(kSmThreads) smk_fwd_kernel(SmArgs a) {
 #pragma unroll
         for (int j = 0; j < kSmNJ; ++j)
           if (v[j] == mx && dd[j] < ld) ld = dd[j];
-        ld = sm_row_min_i(ld);
+        ld = grp_min_i<kSmSub>(ld);
         if (live && sub == 0) fd[s] = ld;
       }
       __syncthreads();
@@ -263,10 +250,10 @@ __global__ void __launch_bounds__(kSmThreads) smk_fwd_kernel(SmArgs a) {
         c[j] = (lt[j] == -INFINITY || dm == -INFINITY) ? -INFINITY : dm + lt[j];
         if (c[j] > lm) { lm = c[j]; ls = sp; }
       }
-      const float M = sm_row_max(lm);
+      const float M = grp_max<kSmSub>(lm);
       float out = M;
       if constexpr (kViterbi) {
-        const int s1 = sm_row_min_i((lm == M && M != -INFINITY) ? ls : 0x7fff);
+        const int s1 = grp_min_i<kSmSub>((lm == M && M != -INFINITY) ? ls : 0x7fff);
         if (live && sub == 0) a.argS[((size_t)b * T + t) * S + s] = (uint8_t)(M == -INFINITY ? 0 : s1);
       } else {
         float se = 0.f;
@@ -412,10 +399,6 @@ __global__ void __launch_bounds__(256) smk_wide_osum_kernel(SwArgs a) {
   }
 }
 
-__device__ __forceinline__ float sw_fresh(const float* p) {  // M rows other waves wrote (L1 bypass)
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // delta(end t, state s, duration d) exactly as smk_fwd_kernel forms it
 __device__ __forceinline__ float sw_delta(const SwArgs& a, int b, int t, int s, int d) {
   const int st = t - d + 1;
@@ -423,28 +406,8 @@ __device__ __forceinline__ float sw_delta(const SwArgs& a, int b, int t, int s, 
   const float o = a.os[(((size_t)b * a.T + t) * a.Dm + (d - 1)) * a.S + s];
   const float u = a.dur[(size_t)s * a.Dm + (d - 1)];
   if (st == 0) return (a.li[s] + o) + u;
-  const float m = sw_fresh(a.Mg + ((size_t)b * a.T + (st - 1)) * a.S + s);
+  const float m = ld_fresh(a.Mg + ((size_t)b * a.T + (st - 1)) * a.S + s);
   return m == -INFINITY ? -INFINITY : (m + o) + u;
-}
-
-// workgroup reductions over kSwNT threads: max of a float; min of an int
-__device__ __forceinline__ float wg_max_sw(float v, float* red) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int k = 1; k < kSwNT / 64; ++k) r = fmaxf(r, red[k]);
-  return r;
-}
-__device__ __forceinline__ int wg_min_sw(int v, int* red) {
-  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = red[0];
-  for (int k = 1; k < kSwNT / 64; ++k) r = min(r, red[k]);
-  return r;
 }
 
 // (max, sum of exp(x - max)) pairs: the online log-sum-exp merge
@@ -521,7 +484,7 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
       }
       __syncthreads();
     }
-    // the M row is read by other waves (sw_fresh, from L2): the stores complete first
+    // the M row is read by other waves (ld_fresh, from L2): the stores complete first
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
@@ -544,7 +507,7 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
     // first (s ascending, d ascending) with the best delta (semi_markov.py:548-556)
     float bv = -INFINITY;
     for (int s = tid; s < S; s += kSwNT) bv = fmaxf(bv, dm[s]);
-    const float best = wg_max_sw(bv, redf);
+    const float best = wg_max<kSwNT>(bv, redf);
     const int nk = S * Dm;
     int bk = 0x7fffffff;
     if (best != -INFINITY)
@@ -552,7 +515,7 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
         const int s = j % S, d = j / S + 1;
         if (sw_delta(a, b, T - 1, s, d) == best) bk = min(bk, s * Dm + d - 1);
       }
-    bk = wg_min_sw(bk, redi);
+    bk = wg_min<kSwNT>(bk, redi);
     int cs = 0, cd = 1;  // every score -inf: the reference's defaults
     if (bk != 0x7fffffff) { cs = bk / Dm; cd = bk % Dm + 1; }
     if (tid == 0) a.scores[b] = best;
@@ -566,7 +529,7 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
       ++k;
       const int tau = t - cd;
       if (tau < 0) break;
-      const float M = sw_fresh(Mrow + (size_t)tau * S + cs);
+      const float M = ld_fresh(Mrow + (size_t)tau * S + cs);
       int ns = 0, nd = 1;
       if (M != -INFINITY) {
         const int dlim = Dm < tau + 1 ? Dm : tau + 1;
@@ -578,7 +541,7 @@ __global__ void __launch_bounds__(kSwNT) smk_wide_kernel(SwArgs a) {
           const float dv = sw_delta(a, b, tau, sp, dp);
           if (lt != -INFINITY && dv != -INFINITY && dv + lt == M) win = min(win, sp * Dm + dp - 1);
         }
-        win = wg_min_sw(win, redi);
+        win = wg_min<kSwNT>(win, redi);
         if (win != 0x7fffffff) { ns = win / Dm; nd = win % Dm + 1; }
       }
       t = tau;

@@ -70,12 +70,6 @@ struct SpGraph {
   const float* w;    // (E) log weight (Viterbi) or probability (sums)
 };
 
-__device__ __forceinline__ int sp_len(const int* lengths, int b, int T) {
-  if (!lengths) return T;
-  const int n = lengths[b];
-  return n < 1 ? 1 : (n > T ? T : n);
-}
-__device__ __forceinline__ int sp_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 inline int sp_pad(int N) { return (N + 63) & ~63; }
 inline int sp_threads(int N) { return N >= kSpMaxNT ? kSpMaxNT : sp_pad(N); }
 
@@ -96,8 +90,8 @@ __device__ __forceinline__ void sp_own_init(SpOwn<D, REG>& o, const SpGraph& g, 
     const int j = tid + d * NT;
     int lo = 0, hi = 0;
     if (j < N) {
-      lo = sp_clamp(g.ptr[j], E);
-      hi = sp_clamp(g.ptr[j + 1], E);
+      lo = clamp_int(g.ptr[j], 0, E);
+      hi = clamp_int(g.ptr[j + 1], 0, E);
       if (hi < lo) hi = lo;
     }
     if (!REG && hi - lo > kSpHub) hi = lo;  // a hub: the waves take it
@@ -108,7 +102,7 @@ __device__ __forceinline__ void sp_own_init(SpOwn<D, REG>& o, const SpGraph& g, 
 #pragma unroll
       for (int r = 0; r < kSpReg<D>; ++r) {
         const bool in = lo + r < hi;
-        o.ro[d][r] = in ? sp_clamp(g.other[lo + r], N - 1) : 0;
+        o.ro[d][r] = in ? clamp_int(g.other[lo + r], 0, N - 1) : 0;
         o.rw[d][r] = in ? g.w[lo + r] : empty;
       }
     }
@@ -119,7 +113,7 @@ __device__ __forceinline__ void sp_own_init(SpOwn<D, REG>& o, const SpGraph& g, 
       for (int j0 = 0; j0 < N; j0 += kWave) {
         const int j = j0 + tid;
         bool h = false;
-        if (j < N) h = sp_clamp(g.ptr[j + 1], E) - sp_clamp(g.ptr[j], E) > kSpHub;
+        if (j < N) h = clamp_int(g.ptr[j + 1], 0, E) - clamp_int(g.ptr[j], 0, E) > kSpHub;
         const unsigned long long m = __ballot(h);
         if (h) hub[n + __popcll(m & ((1ull << tid) - 1ull))] = (uint16_t)j;
         n += __popcll(m);
@@ -154,7 +148,7 @@ __global__ void __launch_bounds__(kSpMaxNT) sp_vit_kernel(SpVitArgs a) {
   float* row = reinterpret_cast<float*>(sp_smem);  // [2][NPAD]
   uint16_t* hub = reinterpret_cast<uint16_t*>(row + 2 * NPAD);
   const int b = blockIdx.x;
-  const int len = sp_len(a.lengths, b, T);
+  const int len = seq_len(a.lengths, b, T);
   const size_t rb = (size_t)b * T;
   SpOwn<D, REG> o;
   sp_own_init(o, a.g, N, E, -INFINITY, hub, &s_nhub);
@@ -166,7 +160,7 @@ __global__ void __launch_bounds__(kSpMaxNT) sp_vit_kernel(SpVitArgs a) {
     const int j = tid + d * NT;
     jc[d] = j < N ? j : 0;
     mine[d] = j < N;
-    if (!REG && j < N) mine[d] = sp_clamp(a.g.ptr[j + 1], E) - sp_clamp(a.g.ptr[j], E) <= kSpHub;
+    if (!REG && j < N) mine[d] = clamp_int(a.g.ptr[j + 1], 0, E) - clamp_int(a.g.ptr[j], 0, E) <= kSpHub;
   }
   float e[D];
   auto load = [&](int q, int d) { return a.obs[(rb + (q < len ? q : len - 1)) * N + jc[d]]; };
@@ -204,7 +198,7 @@ __global__ void __launch_bounds__(kSpMaxNT) sp_vit_kernel(SpVitArgs a) {
       } else {
 #pragma unroll kSpUnroll<D>
         for (int k = o.lo[d]; k < o.hi[d]; ++k) {
-          const int s = sp_clamp(a.g.other[k], N - 1);
+          const int s = clamp_int(a.g.other[k], 0, N - 1);
           const float c = prev[s] + a.g.w[k];
           const bool tk = c > best;
           best = tk ? c : best;
@@ -223,11 +217,11 @@ __global__ void __launch_bounds__(kSpMaxNT) sp_vit_kernel(SpVitArgs a) {
     // the hubs, a wave each in turn (wave-uniform loop)
     for (int h = w; h < nhub; h += NW) {
       const int j = hub[h];
-      const int lo = sp_clamp(a.g.ptr[j], E), hi = sp_clamp(a.g.ptr[j + 1], E);
+      const int lo = clamp_int(a.g.ptr[j], 0, E), hi = clamp_int(a.g.ptr[j + 1], 0, E);
       float best = -INFINITY;
       int arg = 0x7fffffff;
       for (int k = lo + l; k < hi; k += kWave) {
-        const int s = sp_clamp(a.g.other[k], N - 1);
+        const int s = clamp_int(a.g.other[k], 0, N - 1);
         const float c = prev[s] + a.g.w[k];
         const bool tk = c > best;
         best = tk ? c : best;
@@ -304,24 +298,6 @@ __global__ void __launch_bounds__(kSpMaxNT) sp_vit_kernel(SpVitArgs a) {
 }
 
 // -------------------------------------------------------------------------------- sums
-// M_t = max_j obs_t[j] of the valid frames (0 for a row without a finite maximum and in padded
-// frames, which are not read).  One wave per row, grid-stride.
-__global__ void __launch_bounds__(256) sp_row_max_kernel(const float* __restrict__ lo, const int* __restrict__ lengths,
-                                                         int T, int N, size_t rows, float* __restrict__ m) {
-  const int l = threadIdx.x & 63;
-  const size_t nw = ((size_t)gridDim.x * blockDim.x) >> 6;
-  for (size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < rows; row += nw) {
-    const int b = (int)(row / T), t = (int)(row % T);
-    float v = -INFINITY;
-    if (t < sp_len(lengths, b, T)) {
-      const float* src = lo + row * N;
-      for (int j = l; j < N; j += 64) v = fmaxf(v, src[j]);
-      v = wave_max_dpp2(v);
-    }
-    if (l == 0) m[row] = (v > -INFINITY && v < INFINITY) ? v : 0.f;
-  }
-}
-
 // A_e = exp(log_w) in both arc orders, once per call
 __global__ void __launch_bounds__(256) sp_exp_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                      float* __restrict__ oa, float* __restrict__ ob, int E) {
@@ -352,7 +328,7 @@ __device__ __forceinline__ void sp_fb_chain(const SpFbArgs& a, int b, float* row
   const int tid = threadIdx.x, NT = blockDim.x, w = tid >> 6, l = tid & 63, NW = NT >> 6;
   const int N = a.N, T = a.T, E = a.E, NPAD = (N + 63) & ~63;
   const SpGraph& g = CH == 0 ? a.gin : a.gout;
-  const int len = sp_len(a.lengths, b, T);
+  const int len = seq_len(a.lengths, b, T);
   const size_t rb = (size_t)b * T;
   SpOwn<D, REG> o;
   sp_own_init(o, g, N, E, 0.f, hub, s_nhub);
@@ -363,7 +339,7 @@ __device__ __forceinline__ void sp_fb_chain(const SpFbArgs& a, int b, float* row
     const int j = tid + d * NT;
     jc[d] = j < N ? j : 0;
     mine[d] = j < N;
-    if (!REG && j < N) mine[d] = sp_clamp(g.ptr[j + 1], E) - sp_clamp(g.ptr[j], E) <= kSpHub;
+    if (!REG && j < N) mine[d] = clamp_int(g.ptr[j + 1], 0, E) - clamp_int(g.ptr[j], 0, E) <= kSpHub;
   }
   auto tau = [&](int q) { return CH == 0 ? q : len - 1 - q; };  // frame of step q
   auto emis = [&](int q, int j) {
@@ -413,7 +389,7 @@ __device__ __forceinline__ void sp_fb_chain(const SpFbArgs& a, int b, float* row
         for (int r = 0; r < kSpReg<D>; ++r) acc = fmaf(prev[o.ro[d][r]], o.rw[d][r], acc);
       } else {
 #pragma unroll kSpUnroll<D>
-        for (int k = o.lo[d]; k < o.hi[d]; ++k) acc = fmaf(prev[sp_clamp(g.other[k], N - 1)], g.w[k], acc);
+        for (int k = o.lo[d]; k < o.hi[d]; ++k) acc = fmaf(prev[clamp_int(g.other[k], 0, N - 1)], g.w[k], acc);
       }
       if (mine[d]) {
         const int j = jc[d];
@@ -433,9 +409,9 @@ __device__ __forceinline__ void sp_fb_chain(const SpFbArgs& a, int b, float* row
     }
     for (int h = w; h < nhub; h += NW) {
       const int j = hub[h];
-      const int lo = sp_clamp(g.ptr[j], E), hi = sp_clamp(g.ptr[j + 1], E);
+      const int lo = clamp_int(g.ptr[j], 0, E), hi = clamp_int(g.ptr[j + 1], 0, E);
       float acc = 0.f;
-      for (int k = lo + l; k < hi; k += kWave) acc = fmaf(prev[sp_clamp(g.other[k], N - 1)], g.w[k], acc);
+      for (int k = lo + l; k < hi; k += kWave) acc = fmaf(prev[clamp_int(g.other[k], 0, N - 1)], g.w[k], acc);
       acc = wave_sum_dpp(acc);
       if (l == 0) {
         const size_t r = rb + t;
@@ -488,7 +464,7 @@ __global__ void __launch_bounds__(256) sp_scan_kernel(const float* __restrict__ 
   __shared__ double part[256];
   __shared__ double last[256];
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int len = sp_len(lengths, b, T);
+  const int len = seq_len(lengths, b, T);
   const size_t r0 = (size_t)b * T;
   double s = 0.0, u = 0.0;
   for (int t = tid; t < len; t += 256) {
@@ -525,7 +501,7 @@ __global__ void __launch_bounds__(256) sp_post_kernel(const float* __restrict__ 
     const float* u = U + row * N;
     const float* v = V + row * N;
     float iu = 0.f, iv = 0.f, is = 0.f;
-    if (t < sp_len(lengths, b, T)) {
+    if (t < seq_len(lengths, b, T)) {
       float mu = 0.f, mv = 0.f;
       for (int j = l; j < N; j += 64) {
         mu = fmaxf(mu, u[j]);
@@ -592,7 +568,7 @@ __global__ void __launch_bounds__(256) sp_count_kernel(SpCntArgs a) {
   double acc = 0.0;
   for (long long r = r0; r < r1; ++r) {
     const int b = (int)(r / T), t = (int)(r % T);
-    if (t < 1 || t >= sp_len(a.lengths, b, T)) continue;
+    if (t < 1 || t >= seq_len(a.lengths, b, T)) continue;
     const float ca = a.CA[r - 1];
     const float ica = rcp_normal(ca);
     const float left = (a.U[(size_t)(r - 1) * N + sc] * ica) * A;
@@ -757,7 +733,7 @@ HMM355_API int hmm355_sparse_forward_backward_f32(const float* log_obs, const in
   if (workspace_bytes < sp_fb_layout(B, T, N, E, static_cast<char*>(workspace), &w)) return HMM355_E_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t rows = (size_t)B * T;
-  HMM355_TRY(launch(sp_row_max_kernel, dim3(row_grid(rows, 4096)), dim3(256), 0, st, log_obs, lengths, T, N, rows,
+  HMM355_TRY(launch(row_max_kernel<true>, dim3(row_grid(rows, 4096)), dim3(256), 0, st, log_obs, lengths, T, N, rows,
                     w.rmax));
   HMM355_TRY(launch(sp_exp_kernel, dim3((E + 255) / 256), dim3(256), 0, st, in_log_w, out_log_w, w.Ain, w.Aout, E));
   SpFbArgs a{log_obs, {in_ptr, in_src, w.Ain}, {out_ptr, out_dst, w.Aout}, log_p0, lengths,

@@ -41,8 +41,6 @@ constexpr int kBT = 2;        // sequences per workgroup
 constexpr int kWaves = 8;     // input slices per workgroup of a step kernel (one per wave)
 constexpr int kStepThreads = kWaves * 64;
 
-__device__ const double w_logcr_tab[256] = {HMM355_LOGCR_TABLE};
-
 // input slice of one wave: ceil(N / kWaves) rounded up to 4 (slices start 16-B aligned in LDS)
 __host__ __device__ inline int wide_slice(int N) { return (((N + kWaves - 1) / kWaves) + 3) & ~3; }
 
@@ -51,7 +49,7 @@ __host__ __device__ inline int wide_slice(int N) { return (((N + kWaves - 1) / k
 __global__ void __launch_bounds__(256) wide_log_obs_kernel(const float* __restrict__ x, float* __restrict__ lo, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    lo[i] = logcr_fast(x[i] + 1e-8f, w_logcr_tab);
+    lo[i] = logcr_fast(x[i] + 1e-8f, g_logcr_tab);
 }
 
 // ------------------------------------------------------------------------------ Viterbi
@@ -248,20 +246,6 @@ __global__ void __launch_bounds__(256) wide_exp_matrix_kernel(const float* __res
     const float v = expf(log_P[e]);
     A[e] = v;
     AT[j * N + i] = v;
-  }
-}
-
-// M_t = max_j lo_t[j], 0 for a row without a finite maximum (one wave per row, grid-stride)
-__global__ void __launch_bounds__(256) wide_row_max_kernel(const float* __restrict__ lo, int N, size_t rows,
-                                                           float* __restrict__ m) {
-  const int l = threadIdx.x & 63;
-  const size_t nw = ((size_t)gridDim.x * blockDim.x) >> 6;
-  for (size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < rows; row += nw) {
-    const float* src = lo + row * N;
-    float v = -INFINITY;
-    for (int j = l; j < N; j += 64) v = fmaxf(v, src[j]);
-    v = wave_max_dpp2(v);
-    if (l == 0) m[row] = (v > -INFINITY && v < INFINITY) ? v : 0.f;
   }
 }
 
@@ -577,8 +561,8 @@ HMM355_API int hmm355_forward_backward_wide_f32(const float* obs, int obs_mode, 
   HMM355_TRY(launch(wide_exp_matrix_kernel, dim3(stride_blocks((size_t)N * N, 4096)), dim3(256), 0, sm, log_P, N, w.A,
                     w.AT));
   if (obs_mode == HMM355_OBS_LOG) {
-    HMM355_TRY(launch(wide_row_max_kernel, dim3(stride_blocks(rows * 64, 4096)), dim3(256), 0, sm, obs, N, rows,
-                      w.M));
+    HMM355_TRY(launch(row_max_kernel<false>, dim3(stride_blocks(rows * 64, 4096)), dim3(256), 0, sm, obs, nullptr, T, N,
+                      rows, w.M));
   }
   WFbArgs a{obs, w.M, w.A, w.AT, w.U, w.V, w.SA, w.SB, B, T, N, obs_mode};
   HMM355_TRY(launch(wide_fb_init_kernel, dim3(stride_blocks((size_t)B * N, 4096)), dim3(256), 0, sm, a, log_p0));

@@ -17,6 +17,7 @@ def dcd():
 
 
 def kernel(name, idx, op="v_add_f32_e32 v1, v0, v0", vgpr=8, tmp=0):
+    lbb = f".LBB{idx}_1:".ljust(40)   # the compiler pads a label's comment to column 40
     return f"""\t.protected\t{name}
 \t.globl\t{name}
 \t.p2align\t8
@@ -25,7 +26,7 @@ def kernel(name, idx, op="v_add_f32_e32 v1, v0, v0", vgpr=8, tmp=0):
 .Lfunc_begin{idx}:
 ; %bb.0:
 \ts_load_dwordx2 s[0:1], s[4:5], 0x0
-.LBB{idx}_1:                                ; =>This Inner Loop Header: Depth=1
+{lbb}; =>This Inner Loop Header: Depth=1
 \t{op}
 .Ltmp{tmp}:
 \ts_cbranch_scc1 .LBB{idx}_1
@@ -105,6 +106,15 @@ def test_split_finds_every_kind(dcd):
 def test_swapped_order_and_renumbered_labels_compare_equal(dcd):
     b = listing([("_Z2k2Pf", 0, {"tmp": 5}), ("_Z2k1Pf", 1, {"tmp": 9})], cuid="fedcba9876543210")
     assert dcd.compare_text(A, b) == ([], [], [])
+
+
+def test_label_padding_of_a_narrower_function_index_compares_equal(dcd):
+    # a file that loses a kernel ahead of its tenth: index 10 becomes 9, and the padding behind the
+    # label grows by a blank
+    a = listing([("_Z2k1Pf", 10, {})])
+    b = listing([("_Z2k1Pf", 9, {})])
+    assert ".LBB10_1:" + 31 * " " + ";" in a and ".LBB9_1:" + 32 * " " + ";" in b
+    assert dcd.compare_text(a, b) == ([], [], [])
 
 
 def test_changed_instruction_is_reported_under_its_symbol(dcd):

@@ -4,8 +4,7 @@ Build here:  [STAMP_LIB=path] [STAMP_DEFINES="A=1 B=2"] python tools/band_stamps
 (f: the work beside the chains on; items: also the staging helpers' work by item and the psi waves).  Per chain: cycles per step, cycles per step at the block
 barriers (waiting for the helpers), and the clock (s_memtime cycles / s_memrealtime at 100 MHz); the chain's whole blocks by
 part (steps 1 .. 15 | step 0 and the block edge: `edges`); the forward-backward launch's staging waves by chain.
-STAMP_DEFINES="HMM355_BLOCK_EDGE=0" builds the round-11 block loop, "HMM355_STAMP_BAR=0" leaves out the stamps
-round the chain's block barrier."""
+STAMP_DEFINES="HMM355_STAMP_BAR=0" leaves out the stamps round the chain's block barrier."""
 import ctypes
 import os
 import sys

@@ -9,7 +9,8 @@ Per file the listing is split into each @function symbol's body (label to .Lfunc
 .amdhsa_kernel block, each kernel's .amdgpu_metadata entry and each @object symbol's size.  What
 depends only on emission order or on the compile is normalised: the function index in .LBB<n>_<m>,
 .LJTI<n>_<m>, .Lfunc_begin<n>, .Lfunc_end<n> and the BB<n>_<m> of loop comments, the numbers of
-.Ltmp labels (renumbered by first use in the symbol), the __hip_cuid_* symbol; .ident and .file lie
+.Ltmp labels (renumbered by first use in the symbol), the __hip_cuid_* symbol, runs of blanks (the
+padding of a label's comment follows the index's width); .ident and .file lie
 outside every symbol.  The symbols only in A, only in B or different are printed; exit status 1 if
 there are any.  Text is compared: no instruction is named."""
 import os
@@ -22,6 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _INDEXED = re.compile(r"(\.LBB|\bBB|\.LJTI|\.Lfunc_begin|\.Lfunc_end)\d+")
 _TMP = re.compile(r"\.Ltmp\d+")
 _CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
+_BLANKS = re.compile(r"[ \t]+")
 _TYPE = re.compile(r"\.type\s+([^,\s]+),@(function|object)")
 _LABEL = re.compile(r"([A-Za-z_$][\w$.]*):")
 _SIZE = re.compile(r"\.size\s+([^,\s]+),\s*(\d+)$")
@@ -32,7 +34,8 @@ def normalise(lines):
     tmp = {}
     out = []
     for ln in lines:
-        ln = _CUID.sub("__hip_cuid_", _INDEXED.sub(r"\1", ln.strip()))
+        # (blanks: the compiler pads a label's comment to a column, so the padding follows the index's digits)
+        ln = _BLANKS.sub(" ", _CUID.sub("__hip_cuid_", _INDEXED.sub(r"\1", ln.strip())))
         out.append(_TMP.sub(lambda m: tmp.setdefault(m.group(0), ".Ltmp%d" % len(tmp)), ln))
     return out
 
